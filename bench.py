@@ -8,11 +8,23 @@ input that is already resident in HBM:
     predict step : partition search + work-item plan, requests to the leaf owners, per-(query, region)
                    prediction, (u, v) back (RCCL inside libpmk_hip.so), mixture -- for every query of the job
 `value` = patch-solves/s over all ranks (fit steps timed as the contract says: W warm-up steps, K
-timed steps between barrier + synchronize, max over ranks).  predict-points/s is timed the same way
-in a second loop and reported beside it.  N GPUs: weak scaling -- every rank owns `patches` leaves of one
-shared BSP tree and `nq` queries (no data-path collective in fit; one request/response exchange in predict).
+timed steps between barrier + synchronize, max over ranks); `ms_per_step` = milliseconds of one timed fit step.
+N GPUs: weak scaling -- every rank owns `patches` leaves of one shared BSP tree and `nq` queries (no data-path
+collective in fit; one request/response exchange in predict).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C|D|E] [--eps E] [--nq NQ] [--no-cpu]
+A plain run does only what the headline needs: set-up, W warm-up and K timed fit steps, the outputs (--dump-outputs)
+and the result line.  --full adds everything else: predict-points/s (the predict step, timed the same way in a second
+loop), per-stage device times, rooflines, exchange byte counts, config E's fp32-vs-fp64 parity, the end_to_end block
+and the CPU baseline.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C|D|E] [--eps E] [--nq NQ]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-e2e]]
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed on rank 0 as float64 .npy files:
+c.npy (the weights of every patch, concatenated in patch order) and L_sample.npy (a seeded sample of entries of the
+Cholesky factors of a few patches); with --full also y.npy and v.npy (predicted mean and variance of this rank's
+queries).  An array larger than 2^21 values is replaced by a fixed, seeded sample of its entries, so the files stay
+under 64 MB in all.  The inputs are seeded: the same arguments give the same inputs in every run.
 
 Configs (BASELINE.json): C = headline, 256 x 2000 per GPU.  D = 1024 x 2000 over 8 GPUs: 128 leaves and 524 288 queries
 per GPU (run with --gpus 8; `--config D --patches 1024 --nq 4194304` is the whole workload on one GPU).
@@ -108,6 +120,40 @@ def host_cores():
     return cores, aff, quota
 
 
+DUMP_MAX_VALUES = 1 << 21   # per array: 16 MB of float64
+DUMP_SEED = 2024
+
+
+def dump_sample(a, seed):
+    """a, flattened -- or a fixed, seeded sample of DUMP_MAX_VALUES of its entries (in index order) if it is larger"""
+    a = np.ravel(np.asarray(a, dtype=np.float64))
+    if a.size <= DUMP_MAX_VALUES:
+        return a
+    idx = np.random.Generator(np.random.PCG64(seed)).choice(a.size, DUMP_MAX_VALUES, replace=False)
+    return a[np.sort(idx)]
+
+
+def fit_outputs(model, n_patches=4, per_patch=1 << 16):
+    """what a caller of the fit receives: the weights c of every patch and, sampled, the Cholesky factors L"""
+    from patchmixturekriging_amd import mixture as M
+    c = dump_sample(np.concatenate(model.weights()), DUMP_SEED)
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED + 1))
+    patches = np.sort(rng.choice(model.P, min(n_patches, model.P), replace=False))
+    rows = []
+    for r in patches:
+        L = model.get(int(r), M.GET_L)
+        n = L.shape[0]
+        i, j = rng.integers(0, n, per_patch), rng.integers(0, n, per_patch)
+        rows.append(L[np.maximum(i, j), np.minimum(i, j)])          # entries of the lower triangle
+    return {"c": c, "L_sample": np.stack(rows)}
+
+
+def write_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -116,7 +162,12 @@ def main():
     ap.add_argument("--nq", type=int, default=None, help="query points per GPU (default: 2^20; config D: 524288)")
     ap.add_argument("--patches", type=int, default=None, help="patches per GPU (default 256; D: 128; E: 128)")
     ap.add_argument("--n", type=int, default=None, help="points per patch (default 2000; E: 8192)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: predict loop, stage times, rooflines, "
+                         "exchange bytes, config E parity, end_to_end block, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (--full)")
     ap.add_argument("--eps", type=float, default=0.0,
                     help="overlap of the training sets (organizetrainingsets); 0.044 gives the ragged 'realistic' "
                          "variant of config C (n ~ 1.8k-2.2k per patch, SURVEY 8(d))")
@@ -132,8 +183,10 @@ def main():
                     help="which queries a rank holds (request/response exchanges): 'index' = an equal slice of the query "
                          "array; 'home' = the queries whose home leaf it owns (routed once, before the timed region: only "
                          "items that cross a subtree boundary then travel)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end block (reference-named API wall times)")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end block (reference-named API wall times; --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "RANK" not in os.environ and args.gpus > 1:
         # launched plainly (python bench.py --gpus N): start N fresh ranks and relay rank 0's line.  This process has not
@@ -239,6 +292,73 @@ def main():
     dtype = "f32" if cfgE else "f64"
     model = pmk.DeviceModel(X_parts[lo:hi], [y[i] for i in X_parts_inds[lo:hi]], dtype=dtype)
     model.set_bsp(root, lo)
+
+    def sync():
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+
+    def timed(fn, steps, warmup):
+        for _ in range(warmup):
+            fn()
+        sync()
+        t = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        sync()
+        dt = time.perf_counter() - t
+        if world > 1:
+            tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt = float(tt.item())
+        return dt
+
+    # ---------------------------------------------------------------- fit
+    def fit_step():
+        model.fit(th, sigma2)
+
+    dt_fit = timed(fit_step, args.steps, args.warmup)
+    info = model.info()
+    assert np.all(info == 0), "a patch was not positive definite"
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, fit_outputs(model))
+
+    mine = sizes[lo:hi]
+    peak = FP32_PEAK_TFLOPS if cfgE else FP64_PEAK_TFLOPS
+    alg = sum(chol_flops(s) for s in mine)
+    ms = dt_fit / args.steps * 1e3
+    roof_fit = {"bound": "mfma", "achieved": alg / (ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                "frac": alg / (ms * 1e-3) / 1e12 / peak, "note": "algorithmic flops / ms_per_step (K1 + factor + solves)"}
+    metric = {"C": "patch-solves/sec + predict-points/sec, 256 patches x 2k pts",
+              "D": "patch-solves/sec + predict-points/sec, 1024 patches x 2k pts over 8 GPUs (config D: 128 leaves per GPU)",
+              "E": "patch-solves/sec + predict-points/sec, 128 patches x 8k pts (config E)"}[cfg]
+    work = {"C": "mixGP 2-D Spline34(1/15), %d BSP patches x %d points per GPU, sigma2=1e-5 (BASELINE config C)",
+            "D": "mixGP 2-D Spline34(1/15), %d BSP patches x %d points per GPU, sigma2=1e-5 (BASELINE config D shape)",
+            "E": "3-D Spline34(8), %d BSP patches x %d points per GPU, sigma2=1e-3, fp32 (BASELINE config E)"}[cfg] % (P, n)
+
+    if not args.full:
+        # the headline only: predict-points/s and every other figure are measured by --full
+        if rank == 0:
+            print(json.dumps({
+                "metric": metric,
+                "value": P * world * args.steps / dt_fit,
+                "unit": "patch-solves/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": ms,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": dtype, "data": "synthetic", "full": False,
+                "config": {"workload": work,
+                           "patches_per_gpu": P, "points_per_patch": n, "patch_sizes_minmax": [min(sizes), max(sizes)],
+                           "eps": args.eps, "levels": levels, "bsp_build_s": t_bsp},
+                "roofline_fit_step": roof_fit,
+                "kernel_source_hash": kernel_source_hash(),
+            }))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---------------------------------------------------------------- queries and exchange (--full)
     Nq = nq * world
     Xq = rng.uniform(0, 1, (Nq, 3)) if cfgE else np.stack([rng.uniform(-5, 5, Nq), rng.uniform(-10, 10, Nq)], 1)
     replicated = world > 1 and args.exchange.startswith("allgather")
@@ -274,33 +394,6 @@ def main():
                 comm.close()
                 comm, exchange = None, {"abi": "torch", "allgather": "allgather-torch"}[exchange]
 
-    def sync():
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-
-    def timed(fn, steps, warmup):
-        for _ in range(warmup):
-            fn()
-        sync()
-        t = time.perf_counter()
-        for _ in range(steps):
-            fn()
-        sync()
-        dt = time.perf_counter() - t
-        if world > 1:
-            tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = float(tt.item())
-        return dt
-
-    # ---------------------------------------------------------------- fit
-    def fit_step():
-        model.fit(th, sigma2)
-
-    dt_fit = timed(fit_step, args.steps, args.warmup)
-    info = model.info()
-    assert np.all(info == 0), "a patch was not positive definite"
     # per-stage device times (HIP events on the launch stream) of a few extra steps
     nt_max = (max(sizes[lo:hi]) + 127) // 128
     stage_ms = {"kernel_matrix": [], "cholesky": [], "solve": [], "panel": []}
@@ -341,6 +434,10 @@ def main():
     ctx.L.pmk_ctx_enable_timers(ctx.h, 0)
     total_items = predict_step()
     dt_pred = timed(predict_step, args.steps, max(1, args.warmup - 1))
+    if args.dump_outputs and rank == 0:
+        Yd, Vd = query.fetch()
+        write_outputs(args.dump_outputs, {"y": dump_sample(Yd, DUMP_SEED + 2), "v": dump_sample(Vd, DUMP_SEED + 2)})
+        del Yd, Vd
     xbytes = None
     if world > 1:
         if comm is not None:
@@ -400,11 +497,8 @@ def main():
         return
 
     # ---------------------------------------------------------------- rooflines (algorithmic work / device time)
-    mine = sizes[lo:hi]
-    peak = FP32_PEAK_TFLOPS if cfgE else FP64_PEAK_TFLOPS
     esz = 4 if cfgE else 8
     D = X.shape[1]
-    alg = sum(chol_flops(s) for s in mine)
     roof = None
     if "chol_steps" in stage and nt_max > 1:
         launches = len(step_us[0]) if step_us else nt_max - 1
@@ -432,9 +526,6 @@ def main():
             roof["traffic_source"] = pmc_src
         elif pmc is None:
             roof["traffic_source"] = pmc_src
-    ms = dt_fit / args.steps * 1e3
-    roof_fit = {"bound": "mfma", "achieved": alg / (ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
-                "frac": alg / (ms * 1e-3) / 1e12 / peak, "note": "algorithmic flops / ms_per_step (K1 + factor + solves)"}
     roof_k1 = None
     if "kernel_matrix" in stage:
         k1_bytes = sum(esz * (s * (s + 1) / 2 + s * D) for s in mine)
@@ -563,12 +654,6 @@ def main():
                "predict_sample": "%d queries inside the sampled leaves, oracle querymixtureGP! on %d threads" % (len(qs), cores),
                "parity_vs_gpu": {"max_rel_dY": err_y, "max_dV_over_tol": err_v}}
 
-    metric = {"C": "patch-solves/sec + predict-points/sec, 256 patches x 2k pts",
-              "D": "patch-solves/sec + predict-points/sec, 1024 patches x 2k pts over 8 GPUs (config D: 128 leaves per GPU)",
-              "E": "patch-solves/sec + predict-points/sec, 128 patches x 8k pts (config E)"}[cfg]
-    work = {"C": "mixGP 2-D Spline34(1/15), %d BSP patches x %d points per GPU, sigma2=1e-5 (BASELINE config C)",
-            "D": "mixGP 2-D Spline34(1/15), %d BSP patches x %d points per GPU, sigma2=1e-5 (BASELINE config D shape)",
-            "E": "3-D Spline34(8), %d BSP patches x %d points per GPU, sigma2=1e-3, fp32 (BASELINE config E)"}[cfg] % (P, n)
     out = {
         "metric": metric,
         "value": P * world * args.steps / dt_fit,
@@ -577,7 +662,7 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms, "predict_ms_per_step": dt_pred / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": dtype, "data": "synthetic",
+        "dtype": dtype, "data": "synthetic", "full": True,
         "config": {"workload": work,
                    "patches_per_gpu": P, "points_per_patch": n, "patch_sizes_minmax": [min(sizes), max(sizes)],
                    "eps": args.eps, "queries_per_gpu": nq, "radius": radius, "items_per_query": total_items / nq,

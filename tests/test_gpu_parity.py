@@ -1299,7 +1299,7 @@ def test_bench_launched_plainly_with_two_ranks(extra):
     env = dict(os.environ, PMK_BENCH_SHARE_GPU="1", PMK_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--patches", "16",
-           "--n", "600", "--nq", "20000", "--no-cpu"] + extra
+           "--n", "600", "--nq", "20000", "--full", "--no-cpu"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM traffic / L2 hit / issue-stall PMC passes of one bench configuration (run on the GPU box through gpurun):
-#     tools/pmc_passes.sh <outdir> [bench.py args...]
+#     tools/pmc_passes.sh <outdir> [bench.py args...]      (bench.py runs with --full: the predict kernels too)
 # one rocprofv3 --pmc pass per counter group (FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950), each with
 # --kernel-trace only; tools/pmc_reduce.py turns the CSVs into per-kernel, per-launch numbers.
 set -e
@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" \
            "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_LDS"; do
     tag=$(echo "$grp" | tr ' ' '+' | cut -c1-60)
-    echo "== pass $tag: rocprofv3 --pmc $grp --kernel-trace --output-format csv -- python3 bench.py $*" | tee -a "$out/commands.txt"
-    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$out/$tag" -o p -- python3 bench.py "$@" > "$out/$tag.log" 2>&1
+    echo "== pass $tag: rocprofv3 --pmc $grp --kernel-trace --output-format csv -- python3 bench.py --full $*" | tee -a "$out/commands.txt"
+    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$out/$tag" -o p -- python3 bench.py --full "$@" > "$out/$tag.log" 2>&1
     rm -f "$out/$tag"/*kernel_trace.csv
 done
 python3 tools/pmc_reduce.py "$out" > "$out/summary.json"
