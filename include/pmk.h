@@ -220,8 +220,13 @@ int  pmk_query_item_buffers(pmk_query *q, void **u_dev, void **v_dev);
  * which evaluates queryinner! for them and sends (u, v) back into the requester's item buffers.
  * requests of the sorted items [first, first + n) -> DEVICE arrays xq_dev [n x D point-major], region_dev [n] */
 int  pmk_query_export_requests(pmk_query *q, int64_t first, int64_t n, double *xq_dev, int32_t *region_dev);
-/* per-query addend of k(xq, xq) in the predictive variance (the same diagonal term for a query point; NULL clears) */
+/* per-query addend of k(xq, xq) in the predictive variance (the same diagonal term for a query point; host or device
+ * pointer, Nq values; NULL clears) */
 int  pmk_query_set_diag(pmk_query *q, const double *diag);
+/* the addends of the sorted items [first, first + n) -> DEVICE array diag_dev [n] (zeros when the query has none): what a
+ * requester ships with its requests, for the owner's pmk_query_set_diag on the received items.  1 if the query carries
+ * addends, 0 if not.  Enqueues. */
+int  pmk_query_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_dev);
 /* a planned batch of n explicit (point, region) items, one per point (host or device pointers); every region must
  * lie in this model's leaves (-3 otherwise).  Follow with pmk_query_items + pmk_query_export_results. */
 int  pmk_query_create_items(pmk_model *m, int64_t n, const double *xq, const int32_t *region, pmk_query **out);

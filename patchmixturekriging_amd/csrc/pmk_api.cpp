@@ -629,7 +629,7 @@ int pmk_query_set_diag(pmk_query *q, const double *diag)
     dev_free(q->d_qdiag);
     if (!diag || q->Nq == 0) return 0;
     if (dev_alloc(&q->d_qdiag, q->Nq)) return -100;
-    PMK_HIP(hipMemcpy(q->d_qdiag, diag, sizeof(double) * (size_t)q->Nq, hipMemcpyHostToDevice));
+    PMK_HIP(hipMemcpy(q->d_qdiag, diag, sizeof(double) * (size_t)q->Nq, hipMemcpyDefault));   // host or device
     return 0;
 }
 
@@ -1154,6 +1154,17 @@ int pmk_query_export_requests(pmk_query *q, int64_t first, int64_t n, double *xq
     pmk_ctx *c = q->m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     return launch_export_requests(q, first, n, xq_dev, region_dev, c->stream);
+}
+
+int pmk_query_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_dev)
+{
+    if (!q || !q->planned) { set_error("pmk_query_export_request_diag: query is not planned"); return -1; }
+    if (first < 0 || n < 0 || first + n > q->total) { set_error("pmk_query_export_request_diag: bad item range"); return -3; }
+    if (n > 0 && !diag_dev) { set_error("pmk_query_export_request_diag: NULL output"); return -2; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (int rc = launch_export_request_diag(q, first, n, diag_dev, c->stream)) return rc;
+    return q->d_qdiag ? 1 : 0;
 }
 
 int pmk_query_export_results(pmk_query *q, double *u_dev, double *v_dev)

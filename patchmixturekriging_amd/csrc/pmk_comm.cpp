@@ -77,6 +77,7 @@ struct pmk_comm {
     // exchange workspaces on the device, grow only
     int64_t *d_counts = nullptr;          // world (mine) + world * world (table)
     double *d_xs = nullptr, *d_rx = nullptr, *d_ru = nullptr, *d_rv = nullptr;
+    double *d_sd = nullptr, *d_rd = nullptr;  // per-request addends of k(xq, xq) (DPP kernels): sent / received
     int32_t *d_rg = nullptr, *d_rr = nullptr;
     int64_t send_cap = 0, recv_cap = 0;
     int D_cap = 0;
@@ -142,7 +143,7 @@ int pmk_comm_create(pmk_ctx *ctx, int rank, int world, const void *id, pmk_comm 
         delete c;
         return -101;
     }
-    if (hipMalloc((void **)&c->d_counts, sizeof(int64_t) * (size_t)(2 * (world + 1) + world * (world + 1))) != hipSuccess) {
+    if (hipMalloc((void **)&c->d_counts, sizeof(int64_t) * (size_t)((world + 2) * (world + 2))) != hipSuccess) {
         set_error("pmk_comm_create: out of device memory");
         g_rccl.CommDestroy(c->comm);
         delete c;
@@ -157,7 +158,7 @@ void pmk_comm_destroy(pmk_comm *c)
     if (!c) return;
     if (c->remote) pmk_query_destroy(c->remote);
     for (void *p : {(void *)c->d_counts, (void *)c->d_xs, (void *)c->d_rx, (void *)c->d_ru, (void *)c->d_rv, (void *)c->d_rg,
-                    (void *)c->d_rr, (void *)c->d_ag})
+                    (void *)c->d_rr, (void *)c->d_sd, (void *)c->d_rd, (void *)c->d_ag})
         if (p) (void)hipFree(p);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     delete c;
@@ -195,21 +196,23 @@ int pmk_shard_segments(const int64_t *region_offsets, int64_t P_global, int worl
 static int comm_reserve(pmk_comm *c, int D, int64_t nsend, int64_t nrecv)
 {
     if (nsend > c->send_cap || D > c->D_cap) {
-        for (void *p : {(void *)c->d_xs, (void *)c->d_rg}) if (p) (void)hipFree(p);
-        c->d_xs = nullptr; c->d_rg = nullptr; c->send_cap = 0;
+        for (void *p : {(void *)c->d_xs, (void *)c->d_rg, (void *)c->d_sd}) if (p) (void)hipFree(p);
+        c->d_xs = nullptr; c->d_rg = nullptr; c->d_sd = nullptr; c->send_cap = 0;
         const int64_t cap = std::max<int64_t>(nsend + nsend / 8, 1024);
         PMK_HIP(hipMalloc((void **)&c->d_xs, sizeof(double) * (size_t)(cap * MAX_D)));
         PMK_HIP(hipMalloc((void **)&c->d_rg, sizeof(int32_t) * (size_t)cap));
+        PMK_HIP(hipMalloc((void **)&c->d_sd, sizeof(double) * (size_t)cap));
         c->send_cap = cap;
     }
     if (nrecv > c->recv_cap || D > c->D_cap) {
-        for (void *p : {(void *)c->d_rx, (void *)c->d_rr, (void *)c->d_ru, (void *)c->d_rv}) if (p) (void)hipFree(p);
-        c->d_rx = nullptr; c->d_rr = nullptr; c->d_ru = nullptr; c->d_rv = nullptr; c->recv_cap = 0;
+        for (void *p : {(void *)c->d_rx, (void *)c->d_rr, (void *)c->d_ru, (void *)c->d_rv, (void *)c->d_rd}) if (p) (void)hipFree(p);
+        c->d_rx = nullptr; c->d_rr = nullptr; c->d_ru = nullptr; c->d_rv = nullptr; c->d_rd = nullptr; c->recv_cap = 0;
         const int64_t cap = std::max<int64_t>(nrecv + nrecv / 8, 1024);
         PMK_HIP(hipMalloc((void **)&c->d_rx, sizeof(double) * (size_t)(cap * MAX_D)));
         PMK_HIP(hipMalloc((void **)&c->d_rr, sizeof(int32_t) * (size_t)cap));
         PMK_HIP(hipMalloc((void **)&c->d_ru, sizeof(double) * (size_t)cap));
         PMK_HIP(hipMalloc((void **)&c->d_rv, sizeof(double) * (size_t)cap));
+        PMK_HIP(hipMalloc((void **)&c->d_rd, sizeof(double) * (size_t)cap));
         c->recv_cap = cap;
     }
     c->D_cap = MAX_D;
@@ -219,8 +222,10 @@ static int comm_reserve(pmk_comm *c, int D, int64_t nsend, int64_t nrecv)
 // One predict step of a model whose leaves AND queries are sharded over the communicator's ranks
 // (querymixtureGP!, src/RKHS/mixtureGP.jl:159-294, for this rank's queries):
 //   plan of the own queries against the global tree (K5 + sort)
-//   -> the (point, region) requests of every segment of the sorted item list to the rank that owns those leaves
-//   -> queryinner! (K4) for everything received
+//   -> the (point, region) requests of every segment of the sorted item list to the rank that owns those leaves, with
+//      the query's addend of k(xq, xq) when it carries one (DPP kernels, pmk_query_set_diag)
+//   -> queryinner! (K4) for everything received, the addends set on the received items (the strip kernel adds them
+//      before its min_v clamp, exactly as for a query's own items)
 //   -> (u, v) back into the requester's item buffers -> mixture (K6).
 // Everything after the plan is enqueued on the context's stream (RCCL included); the host blocks only where it needs
 // sizes (the plan's counts, the all-gathered segment table, the received items' region offsets).
@@ -251,10 +256,11 @@ int pmk_query_predict_sharded(pmk_query *q, pmk_comm *c, const pmk_kernel_desc *
     }
     PMK_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const int W1 = W + 1;                               // a row of the table: W segment sizes + the rank's status
+    const int W1 = W + 2;                               // a row of the table: W segment sizes + the rank's status + addends?
     std::vector<int64_t> sfirst((size_t)W, 0), row((size_t)W1, 0), table((size_t)(W * W1));
     if (!rc) rc = pmk_shard_segments(q->roff.data(), m->P_global, W, sfirst.data(), row.data());
     row[(size_t)W] = rc;
+    row[(size_t)W + 1] = q->d_qdiag != nullptr;
     int64_t *d_row = c->d_counts, *d_table = c->d_counts + 2 * W1;
     PMK_HIP(hipMemcpyAsync(d_row, row.data(), sizeof(int64_t) * (size_t)W1, hipMemcpyHostToDevice, s));
     PMK_NCCL(g_rccl.AllGather(d_row, d_table, (size_t)W1, ncclInt64, c->comm, s));
@@ -266,12 +272,16 @@ int pmk_query_predict_sharded(pmk_query *q, pmk_comm *c, const pmk_kernel_desc *
             return rc;
         }
     const std::vector<int64_t> &scount = row;
-    std::vector<int64_t> rcount((size_t)W), rfirst((size_t)W);
+    const bool send_diag = q->d_qdiag != nullptr;
+    std::vector<int64_t> rcount((size_t)W), rfirst((size_t)W), rdiag((size_t)W);
     int64_t nrecv = 0;
+    bool recv_diag = false;                                 // some requester ships addends: the received items carry them
     for (int r = 0; r < W; ++r) {
         rcount[(size_t)r] = table[(size_t)(r * W1 + c->rank)];      // what rank r asks of me
+        rdiag[(size_t)r] = table[(size_t)(r * W1 + W + 1)];        // ... and whether its requests carry addends
         rfirst[(size_t)r] = nrecv;
         nrecv += rcount[(size_t)r];
+        recv_diag |= rdiag[(size_t)r] && rcount[(size_t)r] > 0;
     }
     // buffers and the query object of the received requests (recreated when the tree or the dimension changed: its
     // region-offset array is sized by the tree it was created for)
@@ -299,25 +309,40 @@ int pmk_query_predict_sharded(pmk_query *q, pmk_comm *c, const pmk_kernel_desc *
     const int D = m->D;
     // 1. requests out, requests in
     if (q->total > 0 && (rc = launch_export_requests(q, 0, q->total, c->d_xs, c->d_rg, s))) return rc;
+    if (send_diag && (rc = launch_export_request_diag(q, 0, q->total, c->d_sd, s))) return rc;
     PMK_NCCL(g_rccl.GroupStart());
     for (int r = 0; r < W; ++r) {
         if (scount[(size_t)r] > 0) {
             PMK_NCCL_IN_GROUP(g_rccl.Send(c->d_xs + sfirst[(size_t)r] * D, (size_t)(scount[(size_t)r] * D), ncclFloat64, r, c->comm, s));
             PMK_NCCL_IN_GROUP(g_rccl.Send(c->d_rg + sfirst[(size_t)r], (size_t)scount[(size_t)r], ncclInt32, r, c->comm, s));
+            if (send_diag)
+                PMK_NCCL_IN_GROUP(g_rccl.Send(c->d_sd + sfirst[(size_t)r], (size_t)scount[(size_t)r], ncclFloat64, r, c->comm, s));
         }
         if (rcount[(size_t)r] > 0) {
             PMK_NCCL_IN_GROUP(g_rccl.Recv(c->d_rx + rfirst[(size_t)r] * D, (size_t)(rcount[(size_t)r] * D), ncclFloat64, r, c->comm, s));
             PMK_NCCL_IN_GROUP(g_rccl.Recv(c->d_rr + rfirst[(size_t)r], (size_t)rcount[(size_t)r], ncclInt32, r, c->comm, s));
+            if (rdiag[(size_t)r])
+                PMK_NCCL_IN_GROUP(g_rccl.Recv(c->d_rd + rfirst[(size_t)r], (size_t)rcount[(size_t)r], ncclFloat64, r, c->comm, s));
         }
         if (r != c->rank) {
-            c->bytes_sent += scount[(size_t)r] * (8 * D + 4) + rcount[(size_t)r] * 16;
-            c->bytes_recv += rcount[(size_t)r] * (8 * D + 4) + scount[(size_t)r] * 16;
+            c->bytes_sent += scount[(size_t)r] * (8 * D + 4 + (send_diag ? 8 : 0)) + rcount[(size_t)r] * 16;
+            c->bytes_recv += rcount[(size_t)r] * (8 * D + 4 + (rdiag[(size_t)r] ? 8 : 0)) + scount[(size_t)r] * 16;
         }
     }
     PMK_NCCL(g_rccl.GroupEnd());
+    // a requester without addends next to one with them: its items get +0.0, which leaves k(xq, xq) unchanged
+    if (recv_diag)
+        for (int r = 0; r < W; ++r)
+            if (!rdiag[(size_t)r] && rcount[(size_t)r] > 0)
+                PMK_HIP(hipMemsetAsync(c->d_rd + rfirst[(size_t)r], 0, sizeof(double) * (size_t)rcount[(size_t)r], s));
     // 2. queryinner! for everything received
     if ((rc = query_set_items(c->remote, nrecv, c->d_rx, c->d_rr))) return rc;
-    if ((rc = pmk_query_items(c->remote, th))) return rc;
+    // the received items' addends, in received order = the remote query's item order (explicit items: item_query[k] = k).
+    // Borrowed for this launch only: the next step's requesters may have none, and the comm owns the buffer.
+    c->remote->d_qdiag = recv_diag ? c->d_rd : nullptr;
+    rc = pmk_query_items(c->remote, th);
+    c->remote->d_qdiag = nullptr;
+    if (rc) return rc;
     if (nrecv > 0 && (rc = launch_export_results(c->remote, c->d_ru, c->d_rv, s))) return rc;
     // 3. results back, straight into the requester's sorted item buffers
     PMK_NCCL(g_rccl.GroupStart());

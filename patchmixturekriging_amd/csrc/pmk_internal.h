@@ -202,6 +202,7 @@ int launch_plan_fill(pmk_query *q, double radius, double delta, hipStream_t s);
 int launch_sort_items(pmk_query *q, hipStream_t s);
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);
+int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s);
 int launch_export_results(pmk_query *q, double *u_out, double *v_out, hipStream_t s);
 int grow_item_buffers(pmk_query *q, int64_t total);
 int launch_explicit_items(pmk_query *q, int *d_bad, hipStream_t s);

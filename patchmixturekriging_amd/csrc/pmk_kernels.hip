@@ -655,6 +655,26 @@ int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out
     return 0;
 }
 
+// per-query addends of the sorted items [first, first + n) (DPP kernels: they travel with the requests); zeros when the
+// query carries none
+__global__ void export_request_diag_kernel(int64_t first, int64_t n, const int32_t *__restrict__ sorted_item,
+                                           const int32_t *__restrict__ item_query, const double *__restrict__ qdiag,
+                                           double *__restrict__ diag_out)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    diag_out[k] = qdiag ? qdiag[item_query[sorted_item[first + k]]] : 0.0;
+}
+
+int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(export_request_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, first, n,
+                       q->d_sorted_item, q->d_item_query, q->d_qdiag, diag_out);
+    PMK_HIP(hipGetLastError());
+    return 0;
+}
+
 // (u, v) back into item (reference) order
 __global__ void export_results_kernel(int64_t n, const int32_t *__restrict__ item_pos, const double *__restrict__ u,
                                       const double *__restrict__ v, double *__restrict__ u_out, double *__restrict__ v_out)

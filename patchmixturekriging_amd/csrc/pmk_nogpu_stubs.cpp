@@ -35,6 +35,7 @@ int launch_plan_fill(pmk_query *, double, double, hipStream_t) { return no_gpu("
 int launch_sort_items(pmk_query *, hipStream_t) { return no_gpu("launch_sort_items"); }
 int launch_mix(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix"); }
 int launch_export_requests(pmk_query *, int64_t, int64_t, double *, int32_t *, hipStream_t) { return no_gpu("launch_export_requests"); }
+int launch_export_request_diag(pmk_query *, int64_t, int64_t, double *, hipStream_t) { return no_gpu("launch_export_request_diag"); }
 int launch_export_results(pmk_query *, double *, double *, hipStream_t) { return no_gpu("launch_export_results"); }
 int launch_explicit_items(pmk_query *, int *, hipStream_t) { return no_gpu("launch_explicit_items"); }
 int launch_query_mean(const pmk_kernel_desc *, int, int, int64_t, const double *, int64_t, const double *, int64_t, const double *,

@@ -46,16 +46,19 @@ def _comm_device(group=None):
     return "cuda" if dist.get_backend(group) == "nccl" else "cpu"
 
 
-def exchange_counts(send_rows, world, group=None):
-    """send_rows[o] = rows this rank sends to rank o  ->  recv_rows[s] = rows rank s sends to this rank"""
+def exchange_counts(send_rows, world, group=None, flag=None):
+    """send_rows[o] = rows this rank sends to rank o  ->  recv_rows[s] = rows rank s sends to this rank.  With `flag`
+    (an int of this rank, carried in the same all-gather) -> (recv_rows, every rank's flag)"""
     import torch
     import torch.distributed as dist
     dev = _comm_device(group)
-    mine = torch.tensor([int(n) for n in send_rows], dtype=torch.int64, device=dev)
-    table = [torch.zeros(world, dtype=torch.int64, device=dev) for _ in range(world)]
+    extra = [] if flag is None else [int(flag)]
+    mine = torch.tensor([int(n) for n in send_rows] + extra, dtype=torch.int64, device=dev)
+    table = [torch.zeros(world + len(extra), dtype=torch.int64, device=dev) for _ in range(world)]
     dist.all_gather(table, mine, group=group)
     rank = dist.get_rank(group)
-    return [int(table[s][rank]) for s in range(world)]
+    recv_rows = [int(table[s][rank]) for s in range(world)]
+    return recv_rows if flag is None else (recv_rows, [int(table[s][world]) for s in range(world)])
 
 
 def all_to_all_rows(out, inp, out_rows, in_rows, group=None):
@@ -76,14 +79,31 @@ def route_requests(xs, rg, send_rows, world, group=None):
     """xs [total, D] / rg [total]: this rank's requests grouped by owning rank (send_rows[o] rows for rank o, in rank
     order -- the region-sorted item list already is).  Returns (rx, rr, recv_rows): what this rank must evaluate,
     grouped by requesting rank."""
+    rx, rr, _, recv_rows = _route(xs, rg, None, send_rows, world, group, False)
+    return rx, rr, recv_rows
+
+
+def _route(xs, rg, ds, send_rows, world, group, addends):
+    """route_requests, and with `addends` also the requests' addends of k(xq, xq) (ds [total] or None: DPP kernels,
+    DeviceQuery.set_diag).  Every rank of a step must pass the same `addends`.  When any rank ships addends, every rank
+    takes part in one more all-to-all (a rank without them sends zeros, which leave k(xq, xq) unchanged) and rd is what
+    this rank received; otherwise rd is None.  Returns (rx, rr, rd, recv_rows)."""
     import torch
-    recv_rows = exchange_counts(send_rows, world, group)
+    if addends:
+        recv_rows, flags = exchange_counts(send_rows, world, group, flag=ds is not None)
+    else:
+        recv_rows, flags = exchange_counts(send_rows, world, group), [0]
     n = sum(recv_rows)
     rx = torch.empty((n, xs.shape[1]), dtype=xs.dtype, device=xs.device)
     rr = torch.empty(n, dtype=rg.dtype, device=rg.device)
     all_to_all_rows(rx, xs, recv_rows, send_rows, group)
     all_to_all_rows(rr, rg, recv_rows, send_rows, group)
-    return rx, rr, recv_rows
+    rd = None
+    if any(flags):
+        src = ds if ds is not None else torch.zeros(xs.shape[0], dtype=torch.float64, device=xs.device)
+        rd = torch.empty(n, dtype=torch.float64, device=xs.device)
+        all_to_all_rows(rd, src, recv_rows, send_rows, group)
+    return rx, rr, rd, recv_rows
 
 
 def return_results(ru, rv, u_out, v_out, send_rows, recv_rows, group=None):
@@ -146,10 +166,16 @@ def sharded_predict(query, theta, weight_theta, radius, delta, P_global, rank, w
     xs = torch.empty((total, model.D), dtype=torch.float64, device="cuda")
     rg = torch.empty(total, dtype=torch.int32, device="cuda")
     query.export_requests(0, total, xs.data_ptr(), rg.data_ptr())
+    ds = None
+    if query.has_diag:                                  # DPP kernels: the addend of each request's query travels with it
+        ds = torch.empty(total, dtype=torch.float64, device="cuda")
+        query.export_request_diag(0, total, ds.data_ptr())
     handoff()                                           # library stream -> torch / RCCL
-    rx, rr, recv_rows = route_requests(xs, rg, send_rows, world, group)
+    rx, rr, rd, recv_rows = _route(xs, rg, ds, send_rows, world, group, True)
     handoff()
     remote = DeviceQuery.from_items(model, rx.shape[0], rx.data_ptr(), rr.data_ptr())
+    if rd is not None and rx.shape[0] > 0:              # set on the owner: added before the strip kernel's min_v clamp
+        remote.set_diag_device(rd.data_ptr())
     remote.items(theta)
     ru = torch.empty(rx.shape[0], dtype=torch.float64, device="cuda")
     rv = torch.empty(rx.shape[0], dtype=torch.float64, device="cuda")

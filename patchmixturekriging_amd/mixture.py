@@ -157,23 +157,37 @@ class DeviceQuery:
         _lib.check(model.ctx.L.pmk_query_create(model.h, self.Nq, _d(self.Xq), C.byref(h)), "pmk_query_create")
         self.h = h
         self.L = model.ctx.L
+        self.has_diag = False
 
     def set_diag(self, diag):
         """pmk_query_set_diag: per-query addend of k(xq, xq) in the predictive variance (None clears it)"""
         if diag is None:
             _lib.check(self.L.pmk_query_set_diag(self.h, None), "pmk_query_set_diag")
+            self.has_diag = False
             return
         d = np.ascontiguousarray(diag, dtype=np.float64)
         if len(d) != self.Nq:
             raise ValueError("one addend per query point")
         _lib.check(self.L.pmk_query_set_diag(self.h, _d(d)), "pmk_query_set_diag")
+        self.has_diag = True
+
+    def set_diag_device(self, diag_dev_ptr):
+        """pmk_query_set_diag from a device array of Nq float64 (the addends received with a batch of requests)"""
+        _lib.check(self.L.pmk_query_set_diag(self.h, C.cast(C.c_void_p(diag_dev_ptr), _dp)), "pmk_query_set_diag")
+        self.has_diag = True
+
+    def export_request_diag(self, first, n, diag_dev_ptr):
+        """addends of k(xq, xq) of the sorted items [first, first + n) into a caller-owned device array (zeros when the
+        query has none); True if the query carries addends"""
+        return _lib.check(self.L.pmk_query_export_request_diag(self.h, int(first), int(n), diag_dev_ptr),
+                          "pmk_query_export_request_diag") == 1
 
     @classmethod
     def from_items(cls, model, n, xq_ptr, region_ptr):
         """pmk_query_create_items: n explicit (point, region) items received from other ranks; xq_ptr / region_ptr
         are raw host or device addresses (float64 n x D point-major, int32 n)"""
         self = cls.__new__(cls)
-        self.model, self.Xq, self.Nq, self.L = model, None, int(n), model.ctx.L
+        self.model, self.Xq, self.Nq, self.L, self.has_diag = model, None, int(n), model.ctx.L, False
         h = C.c_void_p()
         _lib.check(self.L.pmk_query_create_items(model.h, int(n), xq_ptr, region_ptr, C.byref(h)), "pmk_query_create_items")
         self.h = h

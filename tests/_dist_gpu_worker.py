@@ -25,6 +25,11 @@ def main():
     nq = int(os.environ.get("PMK_TEST_NQ", "3001"))
     Xq = np.stack([rng.uniform(-5, 5, nq), rng.uniform(-10, 10, nq)], 1)
     th, wth = pmk.Spline34KernelType(a), pmk.Spline34KernelType(1 / radius)
+    exchange = os.environ.get("PMK_TEST_EXCHANGE", "requests")
+    dpp = exchange.endswith("-dpp")                # a DPP kernel: the per-query addend travels with the requests
+    if dpp:
+        th = pmk.AdaptiveKernelDPPType(th, lambda x: 0.8 * np.sin(0.7 * x[0]) + 0.1 * x[1])
+        sigma2 = 1e-4
     root, _, _ = pmk.setuppartition(X, levels)
     X_set, X_set_inds, _, _ = pmk.organizetrainingsets(root, levels, X, eps)
     P = len(X_set)
@@ -38,8 +43,11 @@ def main():
     with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
         pd.use_torch_stream(ctx)                    # one stream for the library and torch: no host syncs in the step
         assert pd._shares_current_stream(ctx)
-        model = pmk.DeviceModel(X_set[lo:hi], ys[lo:hi]); model.fit(th, sigma2); model.set_bsp(root, lo)
-        if os.environ.get("PMK_TEST_EXCHANGE", "requests") == "allgather":
+        model = pmk.DeviceModel([pmk.mixture.kernel_points(th, x) for x in X_set[lo:hi]], ys[lo:hi])
+        if dpp:
+            model.set_diag([th.diag_addend(x) for x in X_set[lo:hi]])
+        model.fit(th, sigma2); model.set_bsp(root, lo)
+        if exchange == "allgather":
             # replicated queries: every rank plans all of them and ends with the whole result; its slice is checked
             query = pmk.DeviceQuery(model, Xq)
             for _ in range(2):
@@ -49,7 +57,9 @@ def main():
             total = total if rank == 0 else 0          # the parent adds the ranks' counts
         else:
             q0, q1 = pd.query_range(rank, world, len(Xq))
-            query = pmk.DeviceQuery(model, Xq[q0:q1])
+            query = pmk.DeviceQuery(model, pmk.mixture.kernel_points(th, Xq[q0:q1]))
+            if dpp:
+                query.set_diag(th.diag_addend(Xq[q0:q1]))
             for _ in range(2):                      # twice: buffers are reused across steps
                 total = pd.sharded_predict(query, th, wth, radius, delta, P, rank, world)
             Yq, Vq = query.fetch()

@@ -756,14 +756,15 @@ def _free_port():
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("stream,nq,exchange", [("default", 3001, "requests"), ("side", 3001, "requests"),
                                                 ("default", 200001, "requests"), ("default", 3001, "allgather"),
-                                                ("side", 20001, "allgather")])
+                                                ("side", 20001, "allgather"), ("default", 3001, "requests-dpp")])
 def test_two_ranks_share_one_gpu(tmp_path, stream, nq, exchange):
     """Two fresh child ranks (gloo; both on cuda:0) run patchmixturekriging_amd.dist.sharded_predict -- per-rank
     leaf_base models, region-sorted segments, counts, the two all-to-alls into library-owned device buffers, all on one
     stream with NO host synchronisation in between -- and their slices must equal the single-model result of this
     process bit for bit.  On torch's default stream (handle 0 = the legacy null stream, which the library must be told
     to use explicitly), under a side stream, and on the default stream with an items kernel long enough (200 001
-    queries) that an unordered copy would read its outputs early."""
+    queries) that an unordered copy would read its outputs early.  requests-dpp: a DPP kernel, whose per-query addend of
+    k(xq, xq) must travel with the requests and be added on the owner."""
     import subprocess
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", PMK_TEST_STREAM=stream,
@@ -775,10 +776,18 @@ def test_two_ranks_share_one_gpu(tmp_path, stream, nq, exchange):
     X, y, Xq = _mixgp_case(6000, 4, 0.4, 1 / 4.0, 1e-5, 0.6, 1e-5, nq, 11)
     y = np.sin(X[:, 0]) * np.cos(0.3 * X[:, 1])
     th, wth = pmk.Spline34KernelType(1 / 4.0), pmk.Spline34KernelType(1 / 0.6)
+    sigma2 = 1e-5
+    if exchange.endswith("-dpp"):
+        th, sigma2 = pmk.AdaptiveKernelDPPType(th, lambda x: 0.8 * np.sin(0.7 * x[0]) + 0.1 * x[1]), 1e-4
     root, _, _ = pmk.setuppartition(X, 4)
     X_set, X_set_inds, _, _ = pmk.organizetrainingsets(root, 4, X, 0.4)
-    m = pmk.DeviceModel(X_set, [y[i] for i in X_set_inds]); m.fit(th, 1e-5); m.set_bsp(root, 0)
-    q = pmk.DeviceQuery(m, Xq); total = q.plan(0.6, 1e-5); q.items(th); q.mix(wth)
+    m, _, info = pmk.fit_patches(X_set, [y[i] for i in X_set_inds], th, sigma2)
+    assert np.all(info == 0)
+    m.set_bsp(root, 0)
+    q = pmk.DeviceQuery(m, M.kernel_points(th, Xq))
+    if exchange.endswith("-dpp"):
+        q.set_diag(th.diag_addend(Xq))
+    total = q.plan(0.6, 1e-5); q.items(th); q.mix(wth)
     Y0, V0 = q.fetch()
     tot = 0
     for rank in range(2):
@@ -973,6 +982,29 @@ def test_config_E_fp32_full_size_against_fp64_device_model():
     assert dy.max() <= 1e-4                                           # ~ cond * eps32 on the mean
     assert np.all(dv <= 5e-5 + 2e-3 * V64)                            # the variance is a cancellation 1 - |L^-1 k|^2
     assert np.all(V32 >= 1e-12) and np.all(V32 <= 1 + 1e-6)
+    # fp32 items of one 8192-point patch against queryinner! with the LAPACK fp64 factor of the oracle's U (an independent
+    # fp64 reference, not the device's fp64 model).  kappa(U) ~ 3e5 here; u = (L^-1 k).(L^-1 y) and v = k(x,x) - |L^-1 k|^2
+    # come from triangular solves with L, whose condition number is sqrt(kappa(U)): forward errors sqrt(kappa) eps32
+    # relative to max(1, |u|) and to k(x,x) + |L^-1 k|^2 <= 2
+    import scipy.linalg as sla
+    r, oth = 77, O.kernel(O.SPLINE34, a)
+    U = O.kernel_matrix(oth, X_parts[r]) + sigma2 * np.eye(n)
+    ev = np.linalg.eigvalsh(U)
+    kap = ev[-1] / ev[0]
+    assert ev[0] > 0 and np.sqrt(kap) * eps32 <= 1e-3, kap
+    Lref = sla.cholesky(U, lower=True, check_finite=False)
+    cref = sla.cho_solve((Lref, True), ys[r], check_finite=False)
+    items = np.nonzero(d32["item_region"] == r)[0]
+    assert len(items) >= 8, len(items)
+    qj = np.searchsorted(d32["item_offsets"], items, side="right") - 1
+    worst_u = worst_v = 0.0
+    for i, j in list(zip(items, qj))[:64]:
+        mu, var = O.queryinner(oth, X_parts[r], cref, Lref, Xq[j])
+        worst_u = max(worst_u, abs(d32["item_u"][i] - mu) / max(1, abs(mu)))
+        worst_v = max(worst_v, abs(d32["item_v"][i] - var))
+    print("config E fp32 items of patch %d vs LAPACK fp64: kappa %.3g, max rel du %.2e, max |dv| %.2e (sqrt(kappa) eps32 %.2e)"
+          % (r, kap, worst_u, worst_v, np.sqrt(kap) * eps32))
+    assert worst_u <= 10 * np.sqrt(kap) * eps32 and worst_v <= 20 * np.sqrt(kap) * eps32, (worst_u, worst_v)
 
 
 # ------------------------------------------------------------------------------------ single large problem
