@@ -33,6 +33,7 @@ extern "C" {
 #endif
 
 #define PMK_VERSION 103
+#define PMK_MAX_OUTPUTS 16   /* target columns per patch of the multi-output entry points (pmk_model_set_targets_multi) */
 
 /* kernel families = the isbits kernel structs of src/misc/declarations.jl:18-45,65-67,75-111 */
 enum {
@@ -85,7 +86,7 @@ int  pmk_ctx_set_pipeline(pmk_ctx *ctx, int on);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -274,6 +275,33 @@ void pmk_query_destroy(pmk_query *q);
 int  pmk_predict_mixture(pmk_model *m, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th,
                          int64_t Nq, const double *Xq, double radius, double delta,
                          double *Yq, double *Vq);
+/* ---- multi-output targets: R target columns per patch that share one factor ---------------------------------------
+ * The factor of K + sigma2 I depends only on the points and theta (mixtureGP.jl:99-112), so R fields on the same points
+ * (image channels, vector-field components, a time series on fixed sensors) need one factorisation and R solves.  One
+ * theta and sigma2 for every column.  Not available through the sharded / all-gather exchanges. */
+/* the targets y_parts of fitmixtureGP! (mixtureGP.jl:70-118) as R columns: Y[r] is n[r] x R column-major with leading
+ * dimension ldy[r] >= n[r], 1 <= R <= PMK_MAX_OUTPUTS.  Blocks.  Does not touch the single-output y / z / c. */
+int  pmk_model_set_targets_multi(pmk_model *m, int R, const double *const *Y, const int64_t *ldy);
+/* c = U \ y of fitmixtureGP! (mixtureGP.jl:106) for all R columns of every patch, C = (L L^T)^-1 Y, from the RESIDENT
+ * factor (after pmk_model_fit or pmk_model_load): no refactorisation.  Enqueues. */
+int  pmk_model_solve_multi(pmk_model *m);
+/* blocks; C[r] (n[r] x R column-major, leading dimension ldc[r] >= n[r]) receives the weights of patch r */
+int  pmk_model_get_weights_multi(pmk_model *m, double *const *C, const int64_t *ldc);
+/* stage 2 with R columns, queryinner! (mixtureGP.jl:296-316) for every item: U[item][j] = kq . C[:, j] (no
+ * triangular solve); want_var != 0 also computes v exactly as pmk_query_items does.  The model must hold every leaf.
+ * Enqueues. */
+int  pmk_query_items_multi(pmk_query *q, const pmk_kernel_desc *th, int want_var);
+/* stage 3 with R columns: the mixture weights and blend of pmk_query_mix (mixtureGP.jl:224-272) for every column of U
+ * (and v, if it was computed) for queries [q0, q1).  Enqueues. */
+int  pmk_query_mix_multi(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1);
+/* blocks; Yq: Nq x R column-major with leading dimension ldyq >= Nq; Vq [Nq] or NULL (must be NULL if the items ran
+ * with want_var = 0) */
+int  pmk_query_fetch_multi(pmk_query *q, double *Yq, int64_t ldyq, double *Vq);
+/* one-shot querymixtureGP! (mixtureGP.jl:159-294) with R columns, like pmk_predict_mixture; Vq == NULL skips the
+ * variance (no triangular solve at all): R = 1 without Vq is the mean-only prediction */
+int  pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th, int64_t Nq,
+                               const double *Xq, double radius, double delta, double *Yq, int64_t ldyq, double *Vq);
+
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,
                     const double *c, int64_t Nq, const double *Xq, double *Yq);

@@ -18,7 +18,7 @@ const libpmk = get(ENV, "PMK_LIB",
 
 export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, evalquery,
        setuppartition, getpartitionlines!, organizetrainingsets, fetchhyperplanes,
-       MixtureGPType, MixtureGPDebugType, fitmixtureGP!
+       MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -519,6 +519,63 @@ function querymixtureGP!(Yq::Vector{T}, Vq::Vector{T}, Xq::Vector{Vector{T}}, η
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end
+    return nothing
+end
+
+# ------------------------------------------------------------------------------------------ multi-output targets
+"""fitmixtureGPmulti!(η, Y_parts, θ, σ²) -> C_set: fitmixtureGP! (mixtureGP.jl:70-118) with R target columns per patch
+(Y_parts[r] is n_r x R, 1 <= R <= 16) that share one factor.  The fit runs once on column 1 (η.c_set, η.L_set as
+fitmixtureGP! leaves them); every column is then solved from the resident factor (c = U \\ y of mixtureGP.jl:106 for R
+right-hand sides, pmk_model_solve_multi).  Returns the n_r x R weights of every patch."""
+function fitmixtureGPmulti!(η::MixtureGPType{T}, Y_parts::Vector{Matrix{T}}, θ, σ²::T) where T
+    P = length(η.X_parts)
+    length(Y_parts) == P || throw(ArgumentError("one target matrix per patch"))
+    R = size(Y_parts[1], 2)
+    1 <= R <= 16 || throw(ArgumentError("R = $R target columns, outside 1..16"))
+    for r = 1:P
+        size(Y_parts[r]) == (length(η.X_parts[r]), R) || throw(ArgumentError("patch $r: targets must be n x $R"))
+    end
+    fitmixtureGP!(η, [Y[:, 1] for Y in Y_parts], θ, σ²)
+    Ys = [Matrix{Float64}(Y) for Y in Y_parts]
+    ldy = Int64[size(Y, 1) for Y in Ys]
+    GC.@preserve Ys begin
+        check(ccall((:pmk_model_set_targets_multi, libpmk), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Float64}}, Ptr{Int64}),
+                    η.model, R, [pointer(Y) for Y in Ys], ldy), "pmk_model_set_targets_multi")
+    end
+    check(ccall((:pmk_model_solve_multi, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_solve_multi")
+    Cs = [Matrix{Float64}(undef, size(Y, 1), R) for Y in Ys]
+    GC.@preserve Cs check(ccall((:pmk_model_get_weights_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}),
+                                η.model, [pointer(c) for c in Cs], ldy), "pmk_model_get_weights_multi")
+    return Cs
+end
+
+"""querymixtureGPmulti!(Yq, Vq, Xq, η, root, levels, radius, δ, θ, σ², weight_θ): querymixtureGP! (mixtureGP.jl:159-294)
+for the R columns of fitmixtureGPmulti!.  Yq is Nq x R (R of the fit); Vq is resized to Nq, and Vq === nothing skips the
+variance (no triangular solve: the means need only kq . C, queryinner! of mixtureGP.jl:296-316)."""
+function querymixtureGPmulti!(Yq::Matrix{T}, Vq::Union{Vector{T},Nothing}, Xq::Vector{Vector{T}}, η::MixtureGPType{T}, root,
+                              levels, radius::T, δ::T, θ, σ², weight_θ)::Nothing where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before querymixtureGPmulti!"))
+    Nq = length(Xq); Xm = kpack(θ, Xq)
+    size(Yq, 1) == Nq && 1 <= size(Yq, 2) <= 16 || throw(ArgumentError("Yq must be length(Xq) x R"))
+    Ym = Matrix{Float64}(undef, Nq, 16)          # room for any R <= PMK_MAX_OUTPUTS: the library writes the fit's R columns
+    Vq === nothing || resize!(Vq, Nq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        gq = diagaddend(θ, Xq)
+        gq === nothing || check(ccall((:pmk_query_set_diag, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}), q[], gq), "pmk_query_set_diag")
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_items_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Cint), q[], Ref(desc(θ)),
+                    Vq === nothing ? 0 : 1), "pmk_query_items_multi")
+        check(ccall((:pmk_query_mix_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_multi")
+        check(ccall((:pmk_query_fetch_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], Ym, max(Nq, 1),
+                    Vq === nothing ? Ptr{Float64}(C_NULL) : pointer(Vq)), "pmk_query_fetch_multi")
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+    Yq .= view(Ym, :, 1:size(Yq, 2))
     return nothing
 end
 

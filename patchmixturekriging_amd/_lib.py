@@ -6,6 +6,7 @@ of this module's `lib()` raises, and every operator of the package fails loudly.
 import ctypes as C
 import os
 import subprocess
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -22,8 +23,21 @@ class KernelDesc(C.Structure):
     _fields_ = [("family", C.c_int32), ("flags", C.c_int32), ("p", C.c_double * 4)]
 
 
-def build(force=False, jobs=6):
-    """compile the HIP kernels for gfx950 in-tree (hipcc cross-compiles without a GPU)"""
+def _build_jobs():
+    """parallel compiles: MAX_JOBS if set, else the CPUs this process may run on, at most 16"""
+    env = os.environ.get("MAX_JOBS", "")
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        ncpu = os.cpu_count() or 1
+    return max(1, min(16, ncpu))
+
+
+def build(force=False, jobs=None):
+    """compile the HIP kernels for gfx950 in-tree (hipcc cross-compiles without a GPU); a failed build raises with the
+    end of the compiler output"""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
             if f.endswith((".hip", ".cpp", ".h"))] + [
         os.path.join(_HERE, "..", "include", "pmk.h"), os.path.join(_HERE, "..", "include", "pmk_test.h")]
@@ -32,7 +46,12 @@ def build(force=False, jobs=6):
     if stale:
         if not os.path.exists("/opt/rocm/bin/hipcc"):
             raise PmkError("libpmk_hip.so is missing or stale and hipcc is not available to build it")
-        subprocess.check_call(["make", "-C", CSRC, "-j%d" % jobs, "libpmk_hip.so"])
+        cmd = ["make", "-C", CSRC, "-j%d" % (jobs or _build_jobs()), "libpmk_hip.so"]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        out = r.stdout.decode(errors="replace")
+        if r.returncode != 0:
+            sys.stderr.write(out[-8000:])
+            raise PmkError("building libpmk_hip.so failed (%s, exit %d):\n%s" % (" ".join(cmd), r.returncode, out[-4000:]))
     return SO_PATH
 
 
@@ -116,6 +135,13 @@ SIGNATURES = {
     "pmk_predict_mixture": (C.c_int, [_vp, _kp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp]),
     "pmk_query_mean": (C.c_int, [_vp, _kp, C.c_int, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp]),
     "pmk_query_mean_multi": (C.c_int, [_vp, _kp, C.c_int, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp]),
+    "pmk_model_set_targets_multi": (C.c_int, [_vp, C.c_int, _dpp, _ip]),
+    "pmk_model_solve_multi": (C.c_int, [_vp]),
+    "pmk_model_get_weights_multi": (C.c_int, [_vp, _dpp, _ip]),
+    "pmk_query_items_multi": (C.c_int, [_vp, _kp, C.c_int]),
+    "pmk_query_mix_multi": (C.c_int, [_vp, _kp, C.c_int64, C.c_int64]),
+    "pmk_query_fetch_multi": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
+    "pmk_predict_mixture_multi": (C.c_int, [_vp, _kp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

@@ -474,7 +474,8 @@ void pmk_model_destroy(pmk_model *m)
     dev_free(m->d_order);
     dev_free(m->d_sched);
     dev_free(m->d_sched_init);
-    for (void **p : {&m->d_qtasks, &m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain}) {
+    for (void **p : {&m->d_qtasks, &m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
+                     &m->d_ym, &m->d_cm}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -659,6 +660,7 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     pmk_ctx *c = m->ctx;
     m->th = *th;
     m->sigma2 = sigma2;
+    m->multi_solved = false;            // a new factor: the multi-output weights are stale
     int rc;
     c->tic("fit");
     // Pipelined kernel-matrix build (OFF by default: measured 0.3 ms SLOWER at config C, profiles/r02_fit_experiments.txt;
@@ -998,6 +1000,7 @@ void pmk_query_destroy(pmk_query *q)
     if (q->d_sort_scratch) (void)hipFree(q->d_sort_scratch);
     if (q->d_tasks) (void)hipFree(q->d_tasks);
     if (q->d_sync) (void)hipFree(q->d_sync);
+    dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre);
     delete q;
 }
 
@@ -1055,6 +1058,8 @@ int query_set_items(pmk_query *q, int64_t n, const double *xq, const int32_t *re
     q->Nq = n;
     q->total = n;
     q->planned = false;
+    q->R_items = 0;
+    q->mixed_multi = false;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     q->ntasks = 0;
     if (n > 0) {
@@ -1189,6 +1194,8 @@ int pmk_query_plan(pmk_query *q, double radius, double delta)
     }
     c->tic("plan");
     q->planned = false;
+    q->R_items = 0;
+    q->mixed_multi = false;
     q->total = 0;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     if (q->Nq > 0) {
@@ -1334,6 +1341,201 @@ int pmk_predict_mixture(pmk_model *m, const pmk_kernel_desc *th, const pmk_kerne
     if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items(q, th)) &&
         !(rc = pmk_query_mix(q, weight_th, 0, Nq)))
         rc = pmk_query_fetch(q, Yq, Vq);
+    pmk_query_destroy(q);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------ multi-output targets
+int pmk_model_set_targets_multi(pmk_model *m, int R, const double *const *Y, const int64_t *ldy)
+{
+    if (!m || !Y || !ldy) { set_error("pmk_model_set_targets_multi: NULL argument"); return -1; }
+    if (R < 1 || R > PMK_MAX_OUTPUTS) {
+        set_error("pmk_model_set_targets_multi: R=%d outside 1..%d", R, PMK_MAX_OUTPUTS);
+        return -2;
+    }
+    for (int64_t r = 0; r < m->P; ++r) {
+        if (!Y[r]) { set_error("pmk_model_set_targets_multi: targets of patch %lld are NULL", (long long)r); return -3; }
+        if (ldy[r] < m->desc[(size_t)r].n) {
+            set_error("pmk_model_set_targets_multi: ldy[%lld] = %lld < n = %d", (long long)r, (long long)ldy[r],
+                      m->desc[(size_t)r].n);
+            return -3;
+        }
+    }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+    const size_t count = (size_t)m->tot_y * PMK_MAX_OUTPUTS;
+    if (!m->d_ym) {
+        if (hipMalloc(&m->d_ym, m->esz * count) != hipSuccess || hipMalloc(&m->d_cm, m->esz * count) != hipSuccess) {
+            set_error("pmk_model_set_targets_multi: out of device memory");
+            return -100;
+        }
+    }
+    // row-major blocks of PMK_MAX_OUTPUTS columns (pmk_multi.hip): columns >= R and padding rows stay zero
+    std::vector<double> hy(count, 0.0);
+    for (int64_t r = 0; r < m->P; ++r) {
+        const PatchDesc &d = m->desc[(size_t)r];
+        double *blk = hy.data() + d.yoff * PMK_MAX_OUTPUTS;
+        for (int j = 0; j < R; ++j)
+            for (int64_t i = 0; i < d.n; ++i) blk[i * PMK_MAX_OUTPUTS + j] = Y[r][i + j * ldy[r]];
+    }
+    m->R_multi = 0;
+    m->multi_solved = false;
+    if (int rc = upload_real(m, m->d_ym, 0, hy.data(), count)) return rc;
+    m->R_multi = R;
+    return 0;
+}
+
+int pmk_model_solve_multi(pmk_model *m)
+{
+    if (!m) { set_error("pmk_model_solve_multi: model is NULL"); return -1; }
+    if (!m->fitted) {
+        set_error("pmk_model_solve_multi: no factor (run pmk_model_fit or build the model with pmk_model_load)");
+        return -2;
+    }
+    if (m->R_multi < 1) { set_error("pmk_model_solve_multi: no multi-output targets (pmk_model_set_targets_multi)"); return -3; }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    c->tic("solve_multi");
+    const int rc = PMK_BY_DTYPE(m, launch_solve_multi(m, c->stream));
+    c->toc("solve_multi");
+    if (rc) return rc;
+    m->multi_solved = true;
+    return 0;
+}
+
+int pmk_model_get_weights_multi(pmk_model *m, double *const *C, const int64_t *ldc)
+{
+    if (!m || !C || !ldc) { set_error("pmk_model_get_weights_multi: NULL argument"); return -1; }
+    if (!m->multi_solved) { set_error("pmk_model_get_weights_multi: pmk_model_solve_multi has not run"); return -3; }
+    for (int64_t r = 0; r < m->P; ++r)
+        if (!C[r] || ldc[r] < m->desc[(size_t)r].n) {
+            set_error("pmk_model_get_weights_multi: bad output of patch %lld", (long long)r);
+            return -2;
+        }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    const int64_t count = m->tot_y * PMK_MAX_OUTPUTS;
+    std::vector<double> all((size_t)count);
+    if (int rc = download_real_2d(m, all.data(), count, m->d_cm, 0, count, count, 1, m->ctx->stream)) return rc;
+    for (int64_t r = 0; r < m->P; ++r) {
+        const PatchDesc &d = m->desc[(size_t)r];
+        const double *blk = all.data() + d.yoff * PMK_MAX_OUTPUTS;
+        for (int j = 0; j < m->R_multi; ++j)
+            for (int64_t i = 0; i < d.n; ++i) C[r][i + j * ldc[r]] = blk[i * PMK_MAX_OUTPUTS + j];
+    }
+    return 0;
+}
+
+int pmk_query_items_multi(pmk_query *q, const pmk_kernel_desc *th, int want_var)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_multi: query is not planned"); return -1; }
+    if (!kernel_ok(th)) { set_error("pmk_query_items_multi: unknown kernel family"); return -2; }
+    pmk_model *m = q->m;
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_query_items_multi: the model holds %lld of %lld leaves; multi-output prediction needs a model that "
+                  "holds every leaf", (long long)m->P, (long long)m->P_global);
+        return -4;
+    }
+    if (!m->multi_solved) { set_error("pmk_query_items_multi: pmk_model_solve_multi has not run"); return -3; }
+    if (want_var && !m->fitted) { set_error("pmk_query_items_multi: model is not fitted"); return -3; }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int R = m->R_multi;
+    q->R_items = 0;
+    q->mixed_multi = false;
+    // chunks of 16 items per region (item_means_kernel): prefix over the regions
+    q->mcpre.assign((size_t)m->P + 1, 0);
+    for (int64_t r = 0; r < m->P; ++r)
+        q->mcpre[(size_t)r + 1] = q->mcpre[(size_t)r] + (q->roff[(size_t)r + 1] - q->roff[(size_t)r] + 15) / 16;
+    q->mchunks = q->mcpre[(size_t)m->P];
+    PMK_HIP(hipStreamSynchronize(s));       // earlier launches may still read the buffers replaced below
+    if (q->mcpre_cap < m->P + 1) {
+        dev_free(q->d_mcpre);
+        q->mcpre_cap = 0;
+        if (dev_alloc(&q->d_mcpre, m->P + 1)) return -100;
+        q->mcpre_cap = m->P + 1;
+    }
+    if (q->um_cap < q->total * R) {
+        dev_free(q->d_um);
+        q->um_cap = 0;
+        if (dev_alloc(&q->d_um, q->total * R)) return -100;
+        q->um_cap = q->total * R;
+    }
+    PMK_HIP(hipMemcpyAsync(q->d_mcpre, q->mcpre.data(), sizeof(int64_t) * q->mcpre.size(), hipMemcpyHostToDevice, s));
+    q->R_items = R;
+    c->tic("items_multi");
+    int rc = PMK_BY_DTYPE(m, launch_items_multi(q, *th, s));
+    if (!rc && want_var) rc = PMK_BY_DTYPE(m, launch_items(q, *th, s));      // v exactly as pmk_query_items (u ignored)
+    c->toc("items_multi");
+    if (rc) { q->R_items = 0; return rc; }
+    q->var_items = want_var != 0;
+    return 0;
+}
+
+int pmk_query_mix_multi(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1)
+{
+    if (!q || !q->planned) { set_error("pmk_query_mix_multi: query is not planned"); return -1; }
+    if (q->R_items < 1) { set_error("pmk_query_mix_multi: pmk_query_items_multi has not run on this plan"); return -1; }
+    if (!kernel_ok(weight_th) || weight_th->family >= PMK_BB10) {
+        set_error("pmk_query_mix_multi: the blending profile must be a stationary kernel (evalkernel(tau, theta))");
+        return -2;
+    }
+    if (q0 < 0 || q1 > q->Nq || q0 > q1) { set_error("pmk_query_mix_multi: bad query range"); return -3; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->yqm_cap < q->Nq * q->R_items) {
+        PMK_HIP(hipStreamSynchronize(c->stream));
+        dev_free(q->d_yqm);
+        q->yqm_cap = 0;
+        if (dev_alloc(&q->d_yqm, q->Nq * q->R_items)) return -100;
+        q->yqm_cap = q->Nq * q->R_items;
+    }
+    c->tic("mix_multi");
+    int rc = q->var_items ? launch_mix(q, *weight_th, q0, q1, c->stream) : 0;     // Vq exactly as pmk_query_mix
+    if (!rc) rc = launch_mix_multi(q, *weight_th, q0, q1, c->stream);
+    c->toc("mix_multi");
+    if (rc) return rc;
+    q->mixed_multi = true;
+    return 0;
+}
+
+int pmk_query_fetch_multi(pmk_query *q, double *Yq, int64_t ldyq, double *Vq)
+{
+    if (!q) { set_error("pmk_query_fetch_multi: query is NULL"); return -1; }
+    if (!q->mixed_multi || q->R_items < 1) { set_error("pmk_query_fetch_multi: pmk_query_mix_multi has not run"); return -2; }
+    if (Vq && !q->var_items) {
+        set_error("pmk_query_fetch_multi: Vq was not computed (pmk_query_items_multi ran with want_var = 0)");
+        return -3;
+    }
+    if (Yq && ldyq < q->Nq) { set_error("pmk_query_fetch_multi: ldyq = %lld < Nq = %lld", (long long)ldyq, (long long)q->Nq); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0) {
+        if (Yq)
+            PMK_HIP(hipMemcpy2DAsync(Yq, sizeof(double) * (size_t)ldyq, q->d_yqm, sizeof(double) * (size_t)q->Nq,
+                                     sizeof(double) * (size_t)q->Nq, (size_t)q->R_items, hipMemcpyDeviceToHost, c->stream));
+        if (Vq) PMK_HIP(hipMemcpyAsync(Vq, q->d_vq, sizeof(double) * (size_t)q->Nq, hipMemcpyDeviceToHost, c->stream));
+    }
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th, int64_t Nq,
+                              const double *Xq, double radius, double delta, double *Yq, int64_t ldyq, double *Vq)
+{
+    if (!m) { set_error("pmk_predict_mixture_multi: model is NULL"); return -1; }
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_predict_mixture_multi: the model holds %lld of %lld leaves; multi-output prediction needs a model "
+                  "that holds every leaf", (long long)m->P, (long long)m->P_global);
+        return -4;
+    }
+    if (Yq && ldyq < Nq) { set_error("pmk_predict_mixture_multi: ldyq = %lld < Nq = %lld", (long long)ldyq, (long long)Nq); return -4; }
+    pmk_query *q = nullptr;
+    int rc = pmk_query_create(m, Nq, Xq, &q);
+    if (rc) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_multi(q, th, Vq != nullptr)) &&
+        !(rc = pmk_query_mix_multi(q, weight_th, 0, Nq)))
+        rc = pmk_query_fetch_multi(q, Yq, ldyq, Vq);
     pmk_query_destroy(q);
     return rc;
 }

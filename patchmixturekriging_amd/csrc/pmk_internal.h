@@ -136,6 +136,12 @@ struct pmk_model {
     // prediction strip workspace
     void *d_strip = nullptr;
     int64_t strip_slots = 0;
+    // multi-output targets (pmk_model_set_targets_multi): R columns per patch in row-major tot_y x PMK_MAX_OUTPUTS blocks
+    // (pmk_multi.hip), columns >= R and padding rows zero; C = (L L^T)^-1 Y once pmk_model_solve_multi has run
+    int R_multi = 0;
+    void *d_ym = nullptr;               // targets Y
+    void *d_cm = nullptr;               // weights C (the forward solve's Z in between)
+    bool multi_solved = false;
 };
 
 struct pmk_query {
@@ -168,6 +174,13 @@ struct pmk_query {
     void *d_tasks = nullptr; int64_t ntasks = 0, tasks_cap = 0, strip_grid = 0;
     uint32_t *d_sync = nullptr; int64_t sync_cap = 0, nsync = 0, round_base = 0;   // arrival counters of the strips' lock-step groups   // prediction strip tasks (owned regions)
     bool planned = false;
+    // multi-output prediction (pmk_query_items_multi / _mix_multi): R means per item and per query
+    int R_items = 0;                    // 0: items_multi has not run on the current plan
+    bool var_items = false, mixed_multi = false;
+    double *d_um = nullptr; int64_t um_cap = 0;       // sorted items x R (row-major)
+    double *d_yqm = nullptr; int64_t yqm_cap = 0;     // Nq x R column-major
+    int64_t *d_mcpre = nullptr; int64_t mcpre_cap = 0, mchunks = 0;   // chunks of 16 items per region: prefix [P+1]
+    std::vector<int64_t> mcpre;         // host copy (source of the upload)
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
 };
 
@@ -185,6 +198,8 @@ namespace pmk {
     int set_device_attributes();                                                                                     \
     int build_strip_tasks(pmk_query *q, hipStream_t s);                                                              \
     int launch_items(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                        \
+    int launch_solve_multi(pmk_model *m, hipStream_t s);                                                             \
+    int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                  \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -201,6 +216,7 @@ int launch_plan_count(pmk_query *q, double radius, double delta, hipStream_t s);
 int launch_plan_fill(pmk_query *q, double radius, double delta, hipStream_t s);
 int launch_sort_items(pmk_query *q, hipStream_t s);
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
+int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);
 int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s);
 int launch_export_results(pmk_query *q, double *u_out, double *v_out, hipStream_t s);

@@ -22,6 +22,8 @@ static int no_gpu(const char *what)
     int set_device_attributes() { return 0; }                                                                       \
     int build_strip_tasks(pmk_query *, hipStream_t) { return no_gpu("build_strip_tasks"); }                        \
     int launch_items(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_items"); }         \
+    int launch_solve_multi(pmk_model *, hipStream_t) { return no_gpu("launch_solve_multi"); }                       \
+    int launch_items_multi(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_items_multi"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -34,6 +36,7 @@ int launch_plan_count(pmk_query *, double, double, hipStream_t) { return no_gpu(
 int launch_plan_fill(pmk_query *, double, double, hipStream_t) { return no_gpu("launch_plan_fill"); }
 int launch_sort_items(pmk_query *, hipStream_t) { return no_gpu("launch_sort_items"); }
 int launch_mix(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix"); }
+int launch_mix_multi(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_multi"); }
 int launch_export_requests(pmk_query *, int64_t, int64_t, double *, int32_t *, hipStream_t) { return no_gpu("launch_export_requests"); }
 int launch_export_request_diag(pmk_query *, int64_t, int64_t, double *, hipStream_t) { return no_gpu("launch_export_request_diag"); }
 int launch_export_results(pmk_query *, double *, double *, hipStream_t) { return no_gpu("launch_export_results"); }

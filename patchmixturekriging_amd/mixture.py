@@ -141,6 +141,32 @@ class DeviceModel:
             out = np.transpose(out, (0, 2, 1)).copy()      # column-major blocks -> [block][row][col]
         return out
 
+    def set_targets_multi(self, Y_parts):
+        """pmk_model_set_targets_multi: R target columns per patch (Y_parts[r] is n_r x R, or a vector for R = 1)"""
+        Ys = multi_targets(Y_parts, self.n)
+        R = Ys[0].shape[1]
+        PA = _dp * self.P
+        ldy = np.array([y.shape[0] for y in Ys], dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_set_targets_multi(self.h, R, PA(*[_d(y) for y in Ys]), _i(ldy)),
+                   "pmk_model_set_targets_multi")
+        self.R = R
+
+    def solve_multi(self):
+        """pmk_model_solve_multi: C = (L L^T)^-1 Y for every column from the resident factor (no refactorisation)"""
+        _lib.check(self.ctx.L.pmk_model_solve_multi(self.h), "pmk_model_solve_multi")
+
+    def weights_multi(self):
+        """the n_r x R weights of every patch (one device-to-host transfer)"""
+        R = getattr(self, "R", 0)
+        if R < 1:
+            raise _lib.PmkError("set_targets_multi has not run on this model")
+        out = [np.empty((int(n), R), order="F") for n in self.n]
+        PA = _dp * self.P
+        ldc = np.array([int(n) for n in self.n], dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_get_weights_multi(self.h, PA(*[_d(c) for c in out]), _i(ldc)),
+                   "pmk_model_get_weights_multi")
+        return out
+
     def set_bsp(self, root, leaf_base=0):
         _lib.check(self.ctx.L.pmk_model_set_bsp(self.h, _native(root).h, int(leaf_base)), "pmk_model_set_bsp")
         self.leaf_base = int(leaf_base)
@@ -259,6 +285,24 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_fetch(self.h, _d(Yq), _d(Vq)), "pmk_query_fetch")
         return Yq, Vq
 
+    def items_multi(self, theta, variance=True):
+        d = theta.desc()
+        _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
+        self.variance = bool(variance)
+
+    def mix_multi(self, weight_theta, q0=0, q1=None):
+        d = weight_theta.desc()
+        _lib.check(self.L.pmk_query_mix_multi(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
+                   "pmk_query_mix_multi")
+
+    def fetch_multi(self, R):
+        """(Yq [Nq, R], Vq or None)"""
+        Yq = np.empty((self.Nq, R), order="F")
+        Vq = np.empty(self.Nq) if self.variance else None
+        _lib.check(self.L.pmk_query_fetch_multi(self.h, _d(Yq), max(self.Nq, 1), None if Vq is None else _d(Vq)),
+                   "pmk_query_fetch_multi")
+        return Yq, Vq
+
     def debug(self):
         home = np.empty(self.Nq, dtype=np.int64)
         off = np.empty(self.Nq + 1, dtype=np.int64)
@@ -275,6 +319,33 @@ def kernel_points(theta, X):
     """the points the device evaluates the kernel on: X itself, or X with the warp features appended for the
     closure-carrying kernels (kernels.py: AdaptiveKernelType & co.)"""
     return theta.augment(X) if getattr(theta, "warped", False) else as_points(X)
+
+
+MAX_OUTPUTS = 16      # PMK_MAX_OUTPUTS
+
+
+def multi_targets(Y_parts, n):
+    """validate R-column targets against the patch sizes n -> list of float64 n_r x R Fortran arrays (ValueError before
+    any device call)"""
+    Ys = []
+    for y in Y_parts:
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2:
+            raise ValueError("targets of a patch must be a vector or an n x R matrix")
+        Ys.append(np.asfortranarray(y))
+    if len(Ys) != len(n):
+        raise ValueError("one target matrix per patch: got %d for %d patches" % (len(Ys), len(n)))
+    R = Ys[0].shape[1] if Ys else 0
+    if not 1 <= R <= MAX_OUTPUTS:
+        raise ValueError("R = %d target columns, outside 1..%d" % (R, MAX_OUTPUTS))
+    for r, (y, nr) in enumerate(zip(Ys, n)):
+        if y.shape[0] != int(nr):
+            raise ValueError("patch %d: %d target rows for %d points" % (r, y.shape[0], int(nr)))
+        if y.shape[1] != R:
+            raise ValueError("patch %d: %d target columns, patch 0 has %d" % (r, y.shape[1], R))
+    return Ys
 
 
 def fit_patches(X_parts, y_parts, theta, sigma2, ctx=None, dtype="f64"):
@@ -416,3 +487,36 @@ def queryinner(xq, X, theta, c, L):
         return float(mu[0]), float(max(var[0] + theta.diag_addend(xq)[0], 1e-12))
     mu, var = model.queryinner(0, theta, kernel_points(theta, xq))
     return float(mu[0]), float(var[0])
+
+
+def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
+    """fitmixtureGP! (mixtureGP.jl:70-118) with R target columns per patch that share one factor: the fit runs once on
+    column 0 (c_set, L_set as fitmixtureGP_ leaves them), then every column is solved from the resident factor
+    (c = U \\ y of mixtureGP.jl:106 for R right-hand sides).  Stores eta.C_set (a list of n_r x R)."""
+    Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
+    fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
+    model = eta._model
+    model.set_targets_multi(Ys)
+    model.solve_multi()
+    eta.C_set = model.weights_multi()
+    return eta
+
+
+def querymixtureGP_multi(Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta, variance=True):
+    """querymixtureGP (mixtureGP.jl:120-294) for the R columns of fitmixtureGP_multi_ -> (Yq [Nq, R], Vq or None).
+    variance=False runs no triangular solve: the means need only kq . C (queryinner!, mixtureGP.jl:296-316)."""
+    if eta._model is None or getattr(eta, "C_set", None) is None:
+        raise _lib.PmkError("fitmixtureGP_multi_ must run before querymixtureGP_multi")
+    Xq = np.asarray(Xq, dtype=np.float64)
+    if Xq.ndim == 1:
+        Xq = Xq[None, :]
+    Xq = as_points(Xq)
+    model = eta._model
+    model.set_bsp(root, 0)
+    q = DeviceQuery(model, kernel_points(theta, Xq))
+    if hasattr(theta, "diag_addend"):
+        q.set_diag(theta.diag_addend(Xq))
+    q.plan(radius, delta)
+    q.items_multi(theta, variance)
+    q.mix_multi(weight_theta)
+    return q.fetch_multi(model.R)
