@@ -472,9 +472,7 @@ void pmk_model_destroy(pmk_model *m)
     if (!m) return;
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
     dev_free(m->d_order);
-    dev_free(m->d_sched);
-    dev_free(m->d_sched_init);
-    for (void **p : {&m->d_qtasks, &m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
+    for (void **p : {&m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
                      &m->d_ym, &m->d_cm}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -564,9 +562,6 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
         m->active_prefix.assign((size_t)m->max_nt + 2, 0);
         for (int64_t r = 0; r < P; ++r)
             for (int t = 0; t <= m->desc[(size_t)r].nt; ++t) ++m->active_prefix[(size_t)t];
-        m->order = order;
-        if (const char *e = std::getenv("PMK_CHOL_QUEUE")) m->queue_mode = std::atoi(e) != 0;     // A/B switches
-        if (const char *e = std::getenv("PMK_QUEUE_FROM")) m->queue_from = std::atoi(e);
         if (hipMemcpy(m->d_order, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess) {
             set_error("pmk_model_create: upload failed");
             pmk_model_destroy(m);
@@ -688,11 +683,10 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     } else {
         // Fused kernel-matrix build (PMK_FUSE_K1=0 turns it off): for the compact Spline34 profile in 2 or 3 dimensions K1
         // writes the diagonal 128 x 128 tiles only, and the factorisation's step launches evaluate every tile below them at
-        // its one use instead of reading it from the slab (same kern_eval: the same bits).  Not on the split or queue paths.
+        // its one use instead of reading it from the slab (same kern_eval: the same bits).  Not on the split path.
         const char *fe = std::getenv("PMK_FUSE_K1");
         const bool fuse_env = !(fe && std::atoi(fe) == 0);
-        m->fuse_k1 = fuse_env && th->family == PMK_SPLINE34 && (m->D == 2 || m->D == 3) && !m->split_mode && !m->queue_mode &&
-                     m->max_nt >= 2;
+        m->fuse_k1 = fuse_env && th->family == PMK_SPLINE34 && (m->D == 2 || m->D == 3) && !m->split_mode && m->max_nt >= 2;
         c->tic("kernel_matrix");
         if ((rc = PMK_BY_DTYPE(m, launch_kernel_matrix_slabs(m, *th, sigma2, c->stream, 0, m->P, m->fuse_k1 ? -2 : -1)))) return rc;
         c->toc("kernel_matrix");
@@ -713,10 +707,6 @@ int pmk_model_info(pmk_model *m, int32_t *info)
     if (!m || !info) { set_error("pmk_model_info: NULL argument"); return -1; }
     PMK_HIP(hipSetDevice(m->ctx->device));
     PMK_HIP(hipMemcpyAsync(info, m->d_info, sizeof(int32_t) * (size_t)m->P, hipMemcpyDeviceToHost, m->ctx->stream));
-    constexpr int SCHED_HEADS = 16;                 // pmk_chol.hip: error word, then 8 list heads per segment
-    std::vector<int32_t> sched((size_t)SCHED_HEADS + 8 * 16, 0);
-    if (m->queue_used)
-        PMK_HIP(hipMemcpyAsync(sched.data(), m->d_sched, sizeof(int32_t) * sched.size(), hipMemcpyDeviceToHost, m->ctx->stream));
     int32_t chain_err = 0;
     if (m->chain_used)
         PMK_HIP(hipMemcpyAsync(&chain_err, m->d_chain, sizeof(int32_t), hipMemcpyDeviceToHost, m->ctx->stream));
@@ -726,32 +716,6 @@ int pmk_model_info(pmk_model *m, int32_t *info)
         PMK_HIP(hipMemsetAsync(m->d_chain, 0, sizeof(int32_t), m->ctx->stream));
         set_error("pmk_model_fit: the chained back substitution timed out waiting for block %d", (int)chain_err - 1);
         return -4;
-    }
-    if (m->queue_used) {
-        // the task-queue factorisation: no time-out, and every XCD's list drained
-        bool drained = sched[0] == 0;
-        for (int sg = 0; sg < m->qsegs; ++sg)
-            for (int x = 0; x < 8; ++x)
-                drained = drained && sched[(size_t)SCHED_HEADS + 8 * sg + x] >= m->qoff[(size_t)sg * 9 + x + 1] - m->qoff[(size_t)sg * 9 + x];
-        if (!drained) {
-            if (std::getenv("PMK_QUEUE_DEBUG")) {
-                std::fprintf(stderr, "queue: err %d", sched[0]);
-                for (int x = 0; x < 8; ++x)
-                    std::fprintf(stderr, " | head %d of %d", sched[(size_t)SCHED_HEADS + x], m->qoff[(size_t)x + 1] - m->qoff[(size_t)x]);
-                std::fprintf(stderr, "\n");
-                std::vector<int32_t> fl((size_t)m->P * (size_t)m->qfstride);
-                if (hipMemcpy(fl.data(), m->d_sched + 16 + 8 * 16, sizeof(int32_t) * fl.size(), hipMemcpyDeviceToHost) == hipSuccess)
-                    for (int64_t r = 0; r < m->P; ++r) {
-                        const int32_t *f = fl.data() + (size_t)r * (size_t)m->qfstride;
-                        if (f[0] >= m->desc[(size_t)r].nt) continue;
-                        std::fprintf(stderr, "patch %lld nt %d: diag %d look %d rows", (long long)r, m->desc[(size_t)r].nt, f[0], f[m->qfstride - 1]);
-                        for (int i = 0; i < m->desc[(size_t)r].nt; ++i) std::fprintf(stderr, " %d", f[1 + i]);
-                        std::fprintf(stderr, "\n");
-                    }
-            }
-            set_error("pmk_model_fit: the factorisation's task queue did not complete (error word %d)", sched[0]);
-            return -101;
-        }
     }
     int worst = 0;
     for (int64_t r = 0; r < m->P; ++r) {
