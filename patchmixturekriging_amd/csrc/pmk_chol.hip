@@ -23,7 +23,6 @@
 // read-modify-write.  chol_backsolve_kernel then gives c = L^-T z.
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <numeric>
 
 #include "pmk_mfma.h"
@@ -32,10 +31,7 @@ namespace pmk {
 namespace PMK_NS {
 
 constexpr int PF_CHOL = 4;      // I-operand prefetch depth (k-steps) of the panel GEMM; must divide TILE/4
-#ifndef PMK_PFJ
-#define PMK_PFJ 4
-#endif
-constexpr int PFJ_CHOL = PMK_PFJ;   // J-operand (own rows, HBM) prefetch depth
+constexpr int PFJ_CHOL = 4;     // J-operand (own rows, HBM) prefetch depth
 constexpr int PF_DIAG = 4;
 constexpr int SB = 32;          // sub-block of the in-LDS potrf and of the TRSM block substitution
 
@@ -520,7 +516,7 @@ __global__ __launch_bounds__(256, 2) void chol_step_kernel(const PatchDesc *__re
         const int lid = blockIdx.x;
         if (lid >= nactive * (G + 1)) return;
         if (lid >= nactive * G) {
-            if (nsplit_look == 0) return;                                // PMK_SPLIT_PREREDUCE=0: the factorising workgroup does it
+            if (nsplit_look == 0) return;                                // no fold in this launch: the factorising workgroup does it
             // one more workgroup per patch: the partial tiles of the NEXT diagonal tile (block columns 0..k-1) are folded
             // into the slab here, beside the block rows, instead of by the workgroup that factorises it (whose chain of
             // partial sums + block column k + potrf is what a split step waits for).  Same sums in the same order.
@@ -1047,9 +1043,7 @@ static int reserve_split(pmk_model *m, size_t partial_bytes, size_t solve_bytes)
     return 0;
 }
 
-// col_ev (may be null): event s of the pipelined kernel-matrix build = "stage s is in the slabs"; launch l reads block
-// columns that stages <= l + 1 produced (pmk_kmat.hip), the first kernel reads stage 0
-int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np, const hipEvent_t *col_ev, int n_ev)
+int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
 {
     // gemm_nt consumes K in groups of 4*PF k-indices; K is always a multiple of TILE here
     static_assert(TILE % (4 * PF_DIAG) == 0 && TILE % (4 * PF_CHOL) == 0 && TILE % (4 * PFJ_CHOL) == 0,
@@ -1093,7 +1087,6 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np, const h
     }
     if (half_tiles)
         if (int rc = reserve_split(m, 2 * sizeof(real2_t) * (size_t)PARTIAL_TILE * half_tiles, 0)) return rc;
-    static const bool prereduce = !std::getenv("PMK_SPLIT_PREREDUCE") || std::atoi(std::getenv("PMK_SPLIT_PREREDUCE")) != 0;
     struct Pending { int n, G, nsplit; const real2_t *buf; int l; } pend = {0, 0, 1, nullptr, -1};
     auto flush_pending = [&]() -> int {       // a potrf-only launch (no split step follows the one that left it)
         if (pend.n == 0) return 0;
@@ -1103,7 +1096,6 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np, const h
         pend.n = 0;
         return 0;
     };
-    if (col_ev && n_ev > 0) PMK_HIP(hipStreamWaitEvent(s, col_ev[0], 0));
     hipLaunchKernelGGL(chol_first_kernel, dim3((unsigned)np), dim3(256), 0, s, m->d_desc, (real *)m->d_a, (real *)m->d_inv,
                        (const real *)m->d_y, (real *)m->d_z, m->d_info, m->ctx->d_clk);
     for (int l = 0; l < m->max_nt - 1; ++l) {
@@ -1111,7 +1103,6 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np, const h
         // nt_p >= max_nt - l.  Those patches are a prefix of `order` (sorted by nt, largest first).
         const int nactive = m->active_prefix[(size_t)(m->max_nt - l)];
         const int G = m->max_nt - l - 1;                   // block rows below the diagonal, the same for every active patch
-        if (col_ev && l + 1 < n_ev) PMK_HIP(hipStreamWaitEvent(s, col_ev[l + 1], 0));
         if (nactive == 0) continue;
         if (int rc = ev_begin(l)) return rc;
         const int nsplit = nsplit_of(l, G);
@@ -1126,7 +1117,7 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np, const h
             // patch)?  Only where the workgroup that factorises it is what the NEXT partial launch waits for: its products
             // are short (<= 4 block columns per chunk).  Measured: n = 8192 15.5 -> 14.0 ms; at 16384 and beyond the
             // products are the longer leg and the extra workgroup only stretches this launch (40.0 -> 43.7 ms if always on).
-            const bool fold = prereduce && G >= 2 && (l + 1) <= 4 * nsplit_of(l + 1, G - 1);
+            const bool fold = G >= 2 && (l + 1) <= 4 * nsplit_of(l + 1, G - 1);
             hipLaunchKernelGGL((chol_step_kernel<1, 0>), dim3(grid + (fold ? (unsigned)nactive : 0u)), dim3(256), 0, s, m->d_desc, m->d_order, nactive, G, l,
                                m->max_nt, (real *)m->d_a, (real *)m->d_inv, (const real *)m->d_y, (real *)m->d_z, m->d_info,
                                (const real2_t *)buf, nsplit, m->ctx->d_clk, (const real *)m->d_x, m->th, fold ? nsplit : 0);
@@ -1157,9 +1148,7 @@ static int launch_split_solves(pmk_model *m, hipStream_t s)
 {
     const int P = (int)m->P;
     // one chained launch per solve when the patches' blocks (nearly) fit on the chip together, else block by block
-    static const char *chain_env = std::getenv("PMK_SPLIT_CHAIN");
-    const bool chain = m->chain_mode >= 0 ? m->chain_mode != 0
-                       : chain_env ? std::atoi(chain_env) != 0 : (int64_t)P * m->max_nt <= 2 * (int64_t)m->ctx->num_cu;
+    const bool chain = m->chain_mode >= 0 ? m->chain_mode != 0 : (int64_t)P * m->max_nt <= 2 * (int64_t)m->ctx->num_cu;
     m->chain_used = chain;
     if (chain) {
         const size_t words = 16 + 2 * (size_t)P * (size_t)m->max_nt;          // error word, flags of z, flags of c

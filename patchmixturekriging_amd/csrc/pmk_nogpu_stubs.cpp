@@ -15,8 +15,8 @@ static int no_gpu(const char *what)
 
 #define PMK_STUB_REAL(NS)                                                                                          \
     namespace NS {                                                                                                  \
-    int launch_kernel_matrix_slabs(const pmk_model *, const pmk_kernel_desc &, double, hipStream_t, int64_t, int64_t, int) { return no_gpu("launch_kernel_matrix_slabs"); } \
-    int launch_cholesky(pmk_model *, hipStream_t, int64_t, int64_t, const hipEvent_t *, int) { return no_gpu("launch_cholesky"); } \
+    int launch_kernel_matrix_slabs(const pmk_model *, const pmk_kernel_desc &, double, hipStream_t, int64_t, int64_t, bool) { return no_gpu("launch_kernel_matrix_slabs"); } \
+    int launch_cholesky(pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_cholesky"); }         \
     int launch_backsolve(pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_backsolve"); }       \
     int launch_ninv_from_slabs(pmk_model *, hipStream_t) { return no_gpu("launch_ninv_from_slabs"); }             \
     int set_device_attributes() { return 0; }                                                                       \

@@ -20,8 +20,6 @@
 // row -- timing only, no data is handed over, so a missed rendezvous costs time, never correctness)
 // and the block row of L is then served to all of them by ONE fetch into that XCD's L2.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <tuple>
 
 #include "pmk_mfma.h"
@@ -29,30 +27,15 @@
 namespace pmk {
 namespace PMK_NS {
 
-#ifndef PMK_PFI_PRED
-#define PMK_PFI_PRED 4
-#endif
-constexpr int PF_PRED = PMK_PFI_PRED;       // I-operand (factor, from L2) prefetch depth in k-steps
-#ifndef PMK_PFJ
-#define PMK_PFJ 4
-#endif
-constexpr int PFJ_PRED = PMK_PFJ;   // J-operand (the wave's own strip columns, HBM) prefetch depth
-// column pairs (of 32) per wave: 1 = eight waves of 128 x 32 tiles, two per SIMD (256 registers each); 2 = four waves of
-// 128 x 64 tiles, ONE per SIMD with all 512 registers (accumulators in the AGPR half)
-#ifndef PMK_PRED_NPJ
-#define PMK_PRED_NPJ 1
-#endif
-constexpr int NPJW = PMK_PRED_NPJ;
-constexpr int WCOLS = 32 * NPJW;            // query columns of a wave
+constexpr int PF_PRED = 4;          // I-operand (factor, from L2) prefetch depth in k-steps
+constexpr int PFJ_PRED = 4;         // J-operand (the wave's own strip columns, HBM) prefetch depth
+// a wave owns a 128 x 32 tile of the strip: eight waves, two per SIMD (256 registers each)
+constexpr int WCOLS = 32;           // query columns of a wave
 constexpr int PRED_WAVES = TQ / WCOLS;
 constexpr int PRED_THREADS = 64 * PRED_WAVES;
-typedef real kvec_t __attribute__((ext_vector_type(2 * NPJW)));      // the kernel values of a lane's columns for one row
-#ifndef PMK_SYNC_TICKS
-#define PMK_SYNC_TICKS 4000         // lock-step rendezvous: give up after 40 us (s_memrealtime ticks of 10 ns)
-#endif
-#ifndef PMK_ROUND_TICKS
-#define PMK_ROUND_TICKS 300000      // round barrier: give up after 3 ms, and then for the rest of the launch
-#endif
+constexpr int NC = 2;               // query columns of a lane
+constexpr int SYNC_TICKS = 4000;    // lock-step rendezvous: give up after 40 us (s_memrealtime ticks of 10 ns)
+constexpr int ROUND_TICKS = 300000; // round barrier: give up after 3 ms, and then for the rest of the launch
 
 #ifdef PMK_TRACE
 // diagnostic build only: rendezvous statistics [0] syncs, [1] timeouts, [2] total wait ticks (10 ns), [3] max wait
@@ -86,19 +69,13 @@ struct StripTask {
 
 // one block row of the strip: acc = Kq_i (in) -> -V_i (out)
 template <int NACT>
-__device__ __forceinline__ void strip_block_row(WaveTile<4, NPJW> &acc, const real *Li, int64_t ld, const real *V, int i,
+__device__ __forceinline__ void strip_block_row(WaveTile<4, 1> &acc, const real *Li, int64_t ld, const real *V, int i,
                                                 const real *Lii, const real *ninv_i, int lane, bool traced = false)
 {
     if (i > 0) {
         // order this wave's earlier strip stores before its loads of them
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#ifdef PMK_PRED_POINTER
-        gemm_nt<4, NPJW, PF_PRED, PFJ_PRED, NACT>(acc, Li, ld, V, TQ, i * TILE, lane);
-#elif defined(PMK_PRED_BUF)
-        gemm_nt_buf<4, NPJW, PF_PRED, NACT>(acc, Li, ld, V, TQ, i * TILE, lane);
-#else
-        gemm_nt_indexed<4, NPJW, PF_PRED, PFJ_PRED, NACT>(acc, Li, ld, V, TQ, i * TILE, lane);
-#endif
+        gemm_nt_indexed<4, 1, PF_PRED, PFJ_PRED, NACT>(acc, Li, ld, V, TQ, i * TILE, lane);
     }
 #ifdef PMK_TRACE
     if (traced && i == PMK_TRACE_ROW && lane == 0 && blockIdx.x < 64) {
@@ -108,7 +85,7 @@ __device__ __forceinline__ void strip_block_row(WaveTile<4, NPJW> &acc, const re
 #endif
     // the TRSM operands come straight from the factor (prefetched block by block into registers): no LDS copy, no
     // barrier around staging one
-    tri_solve_global<NPJW>(acc, Lii, ld, ninv_i, lane);
+    tri_solve_global<1>(acc, Lii, ld, ninv_i, lane);
 }
 
 // Kq tile of one block row (query is the first kernel argument, mixtureGP.jl:304) into the wave's accumulator, 32 rows
@@ -116,11 +93,10 @@ __device__ __forceinline__ void strip_block_row(WaveTile<4, NPJW> &acc, const re
 // of a tile and the accumulator they fill were allocated hundreds of spilled registers (scratch traffic was a quarter
 // of this kernel's HBM bytes) and 3 k instructions of code per block row.  Adds the tile's share of the mean.
 template <int D, int FAM>
-__device__ __forceinline__ void eval_tile(WaveTile<4, NPJW> &acc, const real *pt, kvec_t *mine, real *pk, const pmk_kernel_desc &th,
+__device__ __forceinline__ void eval_tile(WaveTile<4, 1> &acc, const real *pt, real2_t *mine, real *pk, const pmk_kernel_desc &th,
                                           int row0, int n, int lane)
 {
-    // the lane's 2 NPJW query points and running means live in its LDS park between block rows (see the kernel)
-    constexpr int NC = 2 * NPJW;
+    // the lane's two query points and running means live in its LDS park between block rows (see the kernel)
     real q[NC][D], mu[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -140,7 +116,7 @@ __device__ __forceinline__ void eval_tile(WaveTile<4, NPJW> &acc, const real *pt
             // padding rows carry coordinates of 1e300 (pack_soa): a compactly supported profile is
             // exactly 0 there, so the Spline34 instantiation needs no bounds test
             const bool inside = (FAM == PMK_SPLINE34) || row0 + r < n;
-            kvec_t kv;
+            real2_t kv;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 kv[c] = inside ? kern_eval<D, FAM, real>(th, q[c], xr) : (real)0;
@@ -150,7 +126,7 @@ __device__ __forceinline__ void eval_tile(WaveTile<4, NPJW> &acc, const real *pt
         }
 #pragma unroll
         for (int sl = 0; sl < 8; ++sl) {
-            const kvec_t kv = mine[sl * 64];
+            const real2_t kv = mine[sl * 64];
 #pragma unroll
             for (int c = 0; c < NC; ++c) acc.f[2 * pi + (sl & 1)][c][sl >> 1] = kv[c];
         }
@@ -169,7 +145,7 @@ __device__ __forceinline__ void eval_tile(WaveTile<4, NPJW> &acc, const real *pt
 //  * the lock-step rendezvous with the other strips of the region is split-phase: thread 0 (wave 0, an early
 //    finisher) arrives for the next block row and spins, bounded, before the barrier.
 template <int D, int FAM>
-__global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip_kernel(const PatchDesc *__restrict__ descs,
+__global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const PatchDesc *__restrict__ descs,
                                                                const real *__restrict__ x, const real *__restrict__ A,
                                                                const real *__restrict__ inv, const real *__restrict__ cvec,
                                                                const StripTask *__restrict__ tasks, int ntasks,
@@ -182,33 +158,20 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
                                                                unsigned long long *__restrict__ clk,
                                                                const double *__restrict__ qdiag)
 {
-    // the wave number as a scalar: everything decided per wave (is the wave active, which block-row variant) is then a
-    // scalar branch, and the buffer resources of the GEMM stay in scalar registers
-#ifdef PMK_PRED_SWAVE
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#endif
     // shader-clock probe: cycles and 10 ns ticks of the lifetime of workgroups 0..7, one per XCD (pmk_ctx_shader_clock)
     unsigned long long c0 = 0, r0 = 0;
     if (clk && blockIdx.x < 8 && threadIdx.x == 0) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
     real *V = strips + (int64_t)blockIdx.x * strip_stride + WCOLS * wave;   // this wave's columns, ld = TQ
     constexpr int PTS = (MAX_D + 1) * TILE;
-    // training points (SoA) and weights of consecutive block rows: a ring of three with one barrier per block row, of six
-    // with one barrier every second block row (PMK_PRED_SYNC2: the older wave of a SIMD then goes straight on into its next
-    // GEMM on odd rows instead of waiting for the younger one's block substitution)
-#ifdef PMK_PRED_SYNC2
-    constexpr int RING = 6;
-#else
+    // training points (SoA) and weights of consecutive block rows: a ring of three with one barrier per block row
     constexpr int RING = 3;
-#endif
     __shared__ real pts[RING * PTS];
-    __shared__ real priv[PRED_WAVES * 8 * 64 * 2 * NPJW];   // lane-private staging of the kernel evaluations (8 slots a lane)
-    kvec_t *mine = reinterpret_cast<kvec_t *>(priv) + (wave * 8) * 64 + lane;
+    __shared__ real priv[PRED_WAVES * 8 * 64 * NC];   // lane-private staging of the kernel evaluations (8 slots a lane)
+    real2_t *mine = reinterpret_cast<real2_t *>(priv) + (wave * 8) * 64 + lane;
     // Per-thread values that are only needed between the MFMA phases (the two query points, the running means and
     // squared norms) are PARKED in LDS: around its GEMM the kernel has no register to spare (128 accumulator + 80 ring
     // registers of 256), and what the compiler spills instead goes to scratch memory, in the middle of the hot loops.
-    constexpr int NC = 2 * NPJW;                   // query columns of a lane
     __shared__ real park[(NC * MAX_D + 2 * NC) * PRED_THREADS];
     real *pk = park + threadIdx.x;      // slot k of this thread: pk[k * PRED_THREADS]
 
@@ -231,7 +194,7 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
                 const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
                 bool ok;
                 while (!(ok = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) &&
-                       __builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)PMK_ROUND_TICKS)
+                       __builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)ROUND_TICKS)
                     __builtin_amdgcn_s_sleep(32);
                 round_sync = ok;
             }
@@ -253,12 +216,12 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
             __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
             while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want &&
-                   __builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)PMK_SYNC_TICKS)
+                   __builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)SYNC_TICKS)
                 __builtin_amdgcn_s_sleep(8);
 #ifdef PMK_TRACE
             const unsigned long long w = __builtin_amdgcn_s_memrealtime() - t0;
             atomicAdd(&g_sync_stats[0], 1ull);
-            if (w >= (unsigned long long)PMK_SYNC_TICKS) atomicAdd(&g_sync_stats[1], 1ull);
+            if (w >= (unsigned long long)SYNC_TICKS) atomicAdd(&g_sync_stats[1], 1ull);
             atomicAdd(&g_sync_stats[2], w);
             atomicMax(&g_sync_stats[3], w);
 #endif
@@ -272,10 +235,10 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
             dst[D * TILE + t] = cr[row];
         };
 
-        // the lane's query columns: 32 pj + 2 (lane & 15) + ej of the wave's WCOLS (padding columns repeat a valid item)
+        // the lane's query columns: 2 (lane & 15) + c of the wave's WCOLS (padding columns repeat a valid item)
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const int col = WCOLS * wave + 32 * (c >> 1) + 2 * (lane & 15) + (c & 1);
+            const int col = WCOLS * wave + 2 * (lane & 15) + c;
             const int64_t p = tk.first + (col < tk.count ? col : 0);
             const int64_t qi = item_query[sorted_item[p]];
 #pragma unroll
@@ -287,29 +250,14 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
         const int last_pairs = (pd.n - (pd.nt - 1) * TILE + 31) >> 5;
 
         __syncthreads();                              // every wave is done with the previous task's points
-#ifdef PMK_PRED_SYNC2
-        if ((int)(threadIdx.x >> 7) < pd.nt) stage_points(threadIdx.x >> 7, threadIdx.x & (TILE - 1));       // rows 0..3
-#else
         if (threadIdx.x < 2 * TILE && (int)(threadIdx.x >> 7) < pd.nt) stage_points(threadIdx.x >> 7, threadIdx.x & (TILE - 1));
-#endif
         if (threadIdx.x == 0 && tk.group >= 0) rendezvous(0);
-        WaveTile<4, NPJW> acc;
+        WaveTile<4, 1> acc;
         bool have = false;                            // acc already holds this block row's kernel tile
         for (int i = 0; i < pd.nt; ++i) {
-#ifdef PMK_PRED_SYNC2
-            // even rows only: rows i .. i + 3 were staged before the barrier before this one; rows i + 4, i + 5 go into the
-            // slots of rows i - 2, i - 1, which every wave has left behind
-            if ((i & 1) == 0) {
-                __syncthreads();
-                if (threadIdx.x < 2 * TILE && i + 4 + (int)(threadIdx.x >> 7) < pd.nt)
-                    stage_points(i + 4 + (int)(threadIdx.x >> 7), threadIdx.x & (TILE - 1));
-            }
-            PMK_PSTAMP(0);
-#else
             __syncthreads();                          // block row i - 1 is complete in every wave; points of row i, i + 1 visible
             PMK_PSTAMP(0);
             if (threadIdx.x < TILE && i + 2 < pd.nt) stage_points(i + 2, threadIdx.x);
-#endif
             if (active) {
                 if (!have) eval_tile<D, FAM>(acc, pts + (i % RING) * PTS, mine, pk, th, i * TILE, pd.n, lane);
                 PMK_PSTAMP(2);
@@ -322,15 +270,10 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
                 const real *Li = S + (int64_t)i * TILE;
                 const real *Lii = Li + (int64_t)i * TILE * ld;
                 const real *ninv_i = inv + pd.ioff + (int64_t)i * 4096;
-#ifdef PMK_PRED_ONE_VARIANT
-                // experiment: one GEMM call site (the last block row computes its identity padding along)
-                strip_block_row<4>(acc, Li, ld, V, i, Lii, ninv_i, lane, PMK_TRACED);
-#else
                 if (i + 1 == pd.nt && last_pairs == 3) strip_block_row<3>(acc, Li, ld, V, i, Lii, ninv_i, lane, PMK_TRACED);
                 else if (i + 1 == pd.nt && last_pairs == 2) strip_block_row<2>(acc, Li, ld, V, i, Lii, ninv_i, lane, PMK_TRACED);
                 else if (i + 1 == pd.nt && last_pairs == 1) strip_block_row<1>(acc, Li, ld, V, i, Lii, ninv_i, lane, PMK_TRACED);
                 else strip_block_row<4>(acc, Li, ld, V, i, Lii, ninv_i, lane, PMK_TRACED);
-#endif
                 PMK_PSTAMP(4);
                 {
                     real vs[NC];
@@ -354,16 +297,13 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
 #pragma unroll
                         for (int qq = 0; qq < 4; ++qq) {
                             const int row = i * TILE + srow + (tile_i(fi, 0, qq) - tile_i(0, 0, 0));
-#pragma unroll
-                            for (int pj = 0; pj < NPJW; ++pj) {
-                                real2_t o;
-                                o[0] = acc.f[fi][2 * pj][qq];
-                                o[1] = acc.f[fi][2 * pj + 1][qq];
-                                __builtin_nontemporal_store(o, reinterpret_cast<real2_t *>(V + (int64_t)row * TQ + 32 * pj + 2 * (lane & 15)));
-                            }
+                            real2_t o;
+                            o[0] = acc.f[fi][0][qq];
+                            o[1] = acc.f[fi][1][qq];
+                            __builtin_nontemporal_store(o, reinterpret_cast<real2_t *>(V + (int64_t)row * TQ + 2 * (lane & 15)));
                         }
                     PMK_PSTAMP(5);
-                    if (NPJW == 1 && wave < PRED_WAVES / 2) {      // the older wave of its SIMD: next tile now, in its idle time
+                    if (wave < PRED_WAVES / 2) {      // the older wave of its SIMD: next tile now, in its idle time
                         eval_tile<D, FAM>(acc, pts + ((i + 1) % RING) * PTS, mine, pk, th, (i + 1) * TILE, pd.n, lane);
                         have = true;
                     }
@@ -378,7 +318,7 @@ __global__ __launch_bounds__(PRED_THREADS, NPJW == 1 ? 2 : 1) void predict_strip
             real a = pk[(NC * D + c) * PRED_THREADS], b = pk[(NC * D + NC + c) * PRED_THREADS];
             a += __shfl_xor(a, 16); b += __shfl_xor(b, 16);
             a += __shfl_xor(a, 32); b += __shfl_xor(b, 32);
-            const int col = WCOLS * wave + 32 * (c >> 1) + 2 * (lane & 15) + (c & 1);
+            const int col = WCOLS * wave + 2 * (lane & 15) + c;
             if ((lane >> 4) == 0 && col < tk.count) {
                 real qe[D];
 #pragma unroll
@@ -432,11 +372,7 @@ int build_strip_tasks(pmk_query *q, hipStream_t s)
         if (e <= b) continue;
         // the region's items are dealt evenly over its strips (not TQ, TQ, ..., remainder): strips of one region then
         // take the same time, which is what keeps them in lock-step
-#ifdef PMK_HALF_STRIPS      /* diagnostic: only waves 0-3 get columns -> one active wave per SIMD */
-        const int64_t nstrips = (e - b + 127) / 128, w = (e - b + nstrips - 1) / nstrips;
-#else
         const int64_t nstrips = (e - b + TQ - 1) / TQ, w = (e - b + nstrips - 1) / nstrips;
-#endif
         for (int64_t f = b; f < e; f += w) {
             StripTask t;
             t.region = (int32_t)r;
@@ -451,13 +387,6 @@ int build_strip_tasks(pmk_query *q, hipStream_t s)
     q->nsync = 0;
     if (tasks.empty()) return 0;
     const int64_t slots = std::min<int64_t>(q->ntasks, (int64_t)m->ctx->num_cu);     // one 8-wave workgroup per CU
-    if (std::getenv("PMK_PRED_DEBUG")) {
-        int64_t cols = 0;
-        for (const StripTask &t : tasks) cols += t.count;
-        std::fprintf(stderr, "strips %lld (%.2f rounds of %lld), %lld items = %.1f %% of their columns, last round %lld strips\n",
-                     (long long)q->ntasks, (double)q->ntasks / (double)slots, (long long)slots, (long long)cols,
-                     100.0 * (double)cols / ((double)q->ntasks * TQ), (long long)(q->ntasks - (q->ntasks - 1) / slots * slots));
-    }
     // lock-step groups: consecutive tasks of one round that land on one XCD and stream the same factor
     {
         int64_t g0 = 0;

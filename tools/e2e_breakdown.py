@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""where the host wall time of fitmixtureGP_ / querymixtureGP_ goes at config C (256 patches x 2000 points, 2^20 queries)
+"""where the host wall time of fitmixtureGP_ / querymixtureGP_ goes, at the size of config C (256 patches x 2000 points,
+2^20 queries) but not its geometry: points and queries uniform in the unit square, Spline34(0.2), radius 0.02
     python tools/e2e_breakdown.py"""
 import os
 import sys
