@@ -151,7 +151,8 @@ int  pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n,
  * per patch K (RKHS.jl:13-34), U = K + sigma2 I, L = chol(U), c = U^-1 y (one Cholesky
  * serves both; the reference's separate LU of :106 is not repeated).  Enqueues only. */
 int  pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2);
-/* blocks; info[P]: 0 ok, k>0 leading minor k not positive definite (PosDefException(k)) */
+/* blocks; info[P]: 0 ok, k>0 leading minor k not positive definite (PosDefException(k)), 1 <= k <= n.  Returns 1 if any
+ * patch failed, 0 if none, < 0 on error (-4: the chained solves timed out, -5: a status word outside 1..n) */
 int  pmk_model_info(pmk_model *m, int32_t *info);
 /* replace the resident targets (same sizes) */
 int  pmk_model_set_targets(pmk_model *m, const double *const *y);

@@ -681,8 +681,14 @@ int pmk_model_info(pmk_model *m, int32_t *info)
     }
     int worst = 0;
     for (int64_t r = 0; r < m->P; ++r) {
-        // a failure inside the identity padding cannot happen; clamp to the patch size for safety
-        if (info[r] > m->desc[(size_t)r].n) info[r] = m->desc[(size_t)r].n;
+        // a failure reported from the identity padding (pivots n+1 .. ld are exactly 1 whatever the patch holds) would be a
+        // wrong tile index or a status word written for the wrong patch: an error, not something to fold into info = n
+        // (tests/test_gpu_breakdown.py plants failures at n - 1 and in the last tile of patches of every size)
+        if (info[r] > m->desc[(size_t)r].n) {
+            set_error("pmk_model_info: patch %lld (n = %d) reports leading minor %d", (long long)r, (int)m->desc[(size_t)r].n,
+                      (int)info[r]);
+            return -5;
+        }
         if (info[r] > 0 && !worst) worst = 1;
     }
     return worst;
