@@ -1,7 +1,7 @@
 """GPU parity matrix over what tests/test_gpu_parity.py checks for the headline case only (Spline34, fp64): every
 kernel family through the generic slab build and the factorisation, D = 1..4, fp32 next to fp64, ragged batches that
 straddle the 64-row slab tiles and the 128-row factor tiles, the fp32 split path, per-family predict strips across
-the 128-column boundary, and DPP kernels through the two exchange forms of the sharded predict.
+the TQ = 256-column strip boundary, and DPP kernels through the two exchange forms of the sharded predict.
 
 References: the CPU oracle (oracle/oracle.py) and LAPACK (scipy.linalg) in fp64.  fp64 is held to the bounds of
 tests/test_gpu_parity.py.  fp32 has no reference semantics (the reference is Float64-only) and is judged by
@@ -16,6 +16,8 @@ import scipy.linalg as sla
 import patchmixturekriging_amd as pmk
 from patchmixturekriging_amd import mixture as M
 from oracle import oracle as O
+
+from _query_refs import blend_reference as _blend_reference, queryinner_reference as _queryinner_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -208,22 +210,11 @@ def test_split_path_fp32_matches_batched_path_and_lapack(P, n, D):
 
 
 # ------------------------------------------------------------------------------------ C. predict parity per family
-def _queryinner_reference(oth, X, c, L, Xq, qdiag=None):
-    """queryinner! for a block of queries: mu = k.c, var = max(k(x,x) + addend - |L^-1 k|^2, 1e-12), and the scales the
-    fp32 bounds use (|k|.|c|, k(x,x) + |L^-1 k|^2)"""
-    K = O.cross_kernel_matrix(oth, X, Xq)                      # n x nq
-    W = sla.solve_triangular(L, K, lower=True, check_finite=False)
-    kxx = np.array([O.kernel_eval(oth, x, x) for x in Xq])
-    if qdiag is not None:
-        kxx = kxx + qdiag
-    w2 = np.einsum("ij,ij->j", W, W)
-    return K.T @ c, np.maximum(kxx - w2, 1e-12), np.abs(K).T @ np.abs(c), np.abs(kxx) + w2
-
-
 @pytest.mark.parametrize("fam,D,dtype", CASES, ids=[_ids(c) for c in CASES])
 def test_predict_strip_parity_matrix(fam, D, dtype):
     """predict_strip_kernel over one region (DeviceModel.queryinner) on the 1-, 129- and 700-point patches of the fit
-    matrix, with query counts around the strip's 128-column boundary, against queryinner! on the device's own factors"""
+    matrix, with query counts around the strip's TQ = 256-column boundary (257 and 513 are dealt over two and three
+    strips), against queryinner! on the device's own factors"""
     f = _fitted(fam, D, dtype)
     model, th, oth = f["model"], f["th"], f["oth"]
     assert np.all(model.info() == 0)
@@ -233,7 +224,7 @@ def test_predict_strip_parity_matrix(fam, D, dtype):
         X = f["Xs"][r]
         c, L = model.get(r, M.GET_C), model.get(r, M.GET_L)
         k = kappa(f["refs"][r][0])
-        for nq in (1, 127, 128, 129, 300):
+        for nq in (1, 127, 128, 129, 255, 256, 257, 300, 513):
             Xq = _points(rng, domain, nq, D)
             if nq >= 127:
                 Xq[:5] = X[:5]                                     # at training points: the variance sits at the floor
@@ -261,16 +252,6 @@ def _mixture_case(seed, N=2400, levels=4, eps=0.3):
     root, _, _ = pmk.setuppartition(X, levels)
     X_set, X_set_inds, _, _ = pmk.organizetrainingsets(root, levels, X, eps)
     return X, [y[i] for i in X_set_inds], Xq, root, X_set
-
-
-def _blend_reference(dbg, per_item_u, per_item_v):
-    Y, V = np.empty(len(dbg["home"])), np.empty(len(dbg["home"]))
-    off = dbg["item_offsets"]
-    for j in range(len(Y)):
-        s = slice(off[j], off[j + 1])
-        w = dbg["item_w"][s] / dbg["item_w"][s].sum()
-        Y[j], V[j] = w @ per_item_u[s], w @ (per_item_v[s] * w)
-    return Y, V
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])

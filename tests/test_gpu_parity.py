@@ -346,7 +346,7 @@ def test_query_edge_cases():
 # ------------------------------------------------------------------------------------ full-size properties
 def test_config_B_and_strip_boundaries():
     # BASELINE config B: 16 BSP patches x 1000 points, fp64 (eps = 0 -> uniform n); enough queries that
-    # regions need several 128-column strips, ragged at the end
+    # regions need several TQ = 256-column strips, dealt evenly over a region
     X, y, Xq = _mixgp_case(16000, 5, 0.0, 1 / 15, 1e-5, 0.3, 1e-5, 6000, 25)
     gpu, ora = _run_both(X, y, Xq, 5, 0.0, 1 / 15, 1e-5, 0.3, 1e-5)
     _compare(gpu, ora)
