@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -297,6 +297,32 @@ int  pmk_query_fetch_multi(pmk_query *q, double *Yq, int64_t ldyq, double *Vq);
  * variance (no triangular solve at all): R = 1 without Vq is the mean-only prediction */
 int  pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th, int64_t Nq,
                                const double *Xq, double radius, double delta, double *Yq, int64_t ldyq, double *Vq);
+
+/* ---- model selection from the resident factor -------------------------------------------------------------------------
+ * Two per-patch scores of a fit at (theta, sigma2), both from what pmk_model_fit leaves on the device (Rasmussen &
+ * Williams, Gaussian Processes for Machine Learning, eq. 5.8 and 5.10-5.12); the reference picks theta and sigma2 by hand
+ * (examples/mixGP.jl:32-35).  With U = K + sigma2 I = L L^T and c = U^-1 y:
+ *   log marginal likelihood of patch r = -1/2 quad - 1/2 logdet - n/2 log(2 pi)
+ *   leave-one-out prediction of training point i from the other n - 1:  y_i - mu_-i = c_i / d_i,  variance 1 / d_i,
+ *   d = diag(U^-1), for every i at once and without refitting.
+ * The scores are PER PATCH: a training point that lies in several overlapping patches has one score in each.  A patch
+ * whose factorisation failed (info != 0) returns NaN in all of logdet, quad, res, var.  Not available through the
+ * sharded / all-gather exchanges. */
+/* blocks. logdet[P]: 2 sum_i log L_ii of every patch (log det of K + sigma2 I); quad[P]: y^T c.
+ * Either may be NULL.  A model built by pmk_model_load holds no targets: quad must be NULL there. */
+int  pmk_model_evidence(pmk_model *m, double *logdet, double *quad);
+/* the same for the R columns of pmk_model_set_targets_multi after pmk_model_solve_multi:
+ * quad[r + P*j] = Y[:,j]^T C[:,j] */
+int  pmk_model_evidence_multi(pmk_model *m, double *logdet, double *quad);
+/* d = diag((L L^T)^-1) of every patch from the RESIDENT factor (after pmk_model_fit or pmk_model_load): the squared
+ * column norms of L^-1, n^3/3 flop per patch on MFMA.  d depends on the factor only: it stays valid until the next
+ * pmk_model_fit, whatever pmk_model_set_weights / pmk_model_solve_multi do to the weights.  Enqueues.  Stage timer "loo". */
+int  pmk_model_loo(pmk_model *m);
+/* blocks. res[r][i] = c_i / d_i (= y_i - mu_-i, so mu_-i = y_i - res[r][i]) from the weights resident at the time of the
+ * call, var[r][i] = 1 / d_i (includes sigma2).  Either may be NULL. */
+int  pmk_model_get_loo(pmk_model *m, double *const *res, double *const *var);
+/* R columns: RES[r] is n[r] x R column-major, leading dimension ldres[r] >= n[r]; var is shared by the columns */
+int  pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ldres, double *const *var);
 
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,

@@ -18,7 +18,8 @@ const libpmk = get(ENV, "PMK_LIB",
 
 export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, evalquery,
        setuppartition, getpartitionlines!, organizetrainingsets, fetchhyperplanes,
-       MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!
+       MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
+       logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -577,6 +578,60 @@ function querymixtureGPmulti!(Yq::Matrix{T}, Vq::Union{Vector{T},Nothing}, Xq::V
     end
     Yq .= view(Ym, :, 1:size(Yq, 2))
     return nothing
+end
+
+# ------------------------------------------------------------------------------------------ model selection
+# Is this (θ, σ²) any good on this patch?  Two scores from the factor that fitmixtureGP! left on the device (Rasmussen &
+# Williams, eq. 5.8 and 5.10-5.12).  Both are PER PATCH: overlapping ε-sets put a training point into several patches, and
+# it has one score in each.  A patch whose factorisation failed returns NaN.
+"""logevidencemixtureGP(η) -> Vector of the P log marginal likelihoods -½ yᵀc - ½ log det(K + σ²I) - (n/2) log 2π"""
+function logevidencemixtureGP(η::MixtureGPType{T}) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before logevidencemixtureGP"))
+    P = length(η.X_parts)
+    logdet = Vector{Float64}(undef, P); quad = Vector{Float64}(undef, P)
+    check(ccall((:pmk_model_evidence, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), η.model, logdet, quad),
+          "pmk_model_evidence")
+    return [-0.5 * quad[r] - 0.5 * logdet[r] - 0.5 * length(η.X_parts[r]) * log(2π) for r = 1:P]
+end
+
+"""logevidencemixtureGPmulti(η, R) -> P x R matrix, for the R columns of fitmixtureGPmulti! (one log det per patch
+serves every column)"""
+function logevidencemixtureGPmulti(η::MixtureGPType{T}, R::Integer) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before logevidencemixtureGPmulti"))
+    1 <= R <= 16 || throw(ArgumentError("R = $R target columns, outside 1..16"))
+    P = length(η.X_parts)
+    logdet = Vector{Float64}(undef, P); quad = Matrix{Float64}(undef, P, 16)    # room for any R <= PMK_MAX_OUTPUTS
+    check(ccall((:pmk_model_evidence_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), η.model, logdet, quad),
+          "pmk_model_evidence_multi")
+    return [-0.5 * quad[r, j] - 0.5 * logdet[r] - 0.5 * length(η.X_parts[r]) * log(2π) for r = 1:P, j = 1:R]
+end
+
+"""loomixtureGP(η) -> (res_set, var_set): leave-one-out residuals and variances of every training point of every patch,
+from one pass over the resident factor (no refit).  res_set[r][i] = yᵢ - μ₋ᵢ (so μ₋ᵢ = yᵢ - res_set[r][i]);
+var_set[r][i] is the predictive variance of yᵢ from the other n_r - 1 points of patch r, noise included."""
+function loomixtureGP(η::MixtureGPType{T}) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before loomixtureGP"))
+    check(ccall((:pmk_model_loo, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_loo")
+    res = [Vector{Float64}(undef, length(X)) for X in η.X_parts]
+    var = [Vector{Float64}(undef, length(X)) for X in η.X_parts]
+    GC.@preserve res var check(ccall((:pmk_model_get_loo, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}),
+                                     η.model, [pointer(a) for a in res], [pointer(a) for a in var]), "pmk_model_get_loo")
+    return res, var
+end
+
+"""loomixtureGPmulti(η, R) -> (RES_set, var_set) for the R columns of fitmixtureGPmulti!: RES_set[r] is n_r x R, the
+variances are shared by the columns"""
+function loomixtureGPmulti(η::MixtureGPType{T}, R::Integer) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before loomixtureGPmulti"))
+    1 <= R <= 16 || throw(ArgumentError("R = $R target columns, outside 1..16"))
+    check(ccall((:pmk_model_loo, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_loo")
+    RES = [Matrix{Float64}(undef, length(X), 16) for X in η.X_parts]            # room for any R <= PMK_MAX_OUTPUTS
+    var = [Vector{Float64}(undef, length(X)) for X in η.X_parts]
+    ldres = Int64[size(A, 1) for A in RES]
+    GC.@preserve RES var check(ccall((:pmk_model_get_loo_multi, libpmk), Cint,
+                                     (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
+                                     η.model, [pointer(A) for A in RES], ldres, [pointer(a) for a in var]), "pmk_model_get_loo_multi")
+    return [A[:, 1:R] for A in RES], var
 end
 
 # ------------------------------------------------------------------------------------------ multi-GPU (one process per GPU)

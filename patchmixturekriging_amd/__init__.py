@@ -14,7 +14,8 @@ from .kernels import (AdaptiveKernelDPPType, AdaptiveKernelMultiWarpDPPType, Ada
                       Spline12KernelType, Spline32KernelType, Spline34KernelType, StationaryKernelType,
                       TunableRationalQuadraticKernelType)
 from .mixture import (DeviceModel, DeviceQuery, MixtureGPDebugType, MixtureGPType,   # noqa: F401
-                      PosDefException, fit_patches, fitmixtureGP_, fitmixtureGP_multi_, queryinner, querymixtureGP,
+                      PosDefException, fit_patches, fitmixtureGP_, fitmixtureGP_multi_, logevidencemixtureGP,
+                      logevidencemixtureGP_multi, loomixtureGP, loomixtureGP_multi, queryinner, querymixtureGP,
                       querymixtureGP_, querymixtureGP_multi)
 from .partition import (BinaryNode, HyperplaneType, PartitionDataType, array2matrix,  # noqa: F401
                         convert2itpindex, fetchhyperplanes, findneighbourpartitions, findpartition,

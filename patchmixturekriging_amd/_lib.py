@@ -141,6 +141,11 @@ SIGNATURES = {
     "pmk_query_mix_multi": (C.c_int, [_vp, _kp, C.c_int64, C.c_int64]),
     "pmk_query_fetch_multi": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
     "pmk_predict_mixture_multi": (C.c_int, [_vp, _kp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp]),
+    "pmk_model_evidence": (C.c_int, [_vp, _dp, _dp]),
+    "pmk_model_evidence_multi": (C.c_int, [_vp, _dp, _dp]),
+    "pmk_model_loo": (C.c_int, [_vp]),
+    "pmk_model_get_loo": (C.c_int, [_vp, _dpp, _dpp]),
+    "pmk_model_get_loo_multi": (C.c_int, [_vp, _dpp, _ip, _dpp]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

@@ -113,6 +113,19 @@ static void pack_soa(int D, int64_t n, int64_t ld, const double *X, double *out)
     }
 }
 
+// the strip workspace of the model: one max_nt * TILE x TQ block per workgroup slot of a strip kernel (prediction,
+// leave-one-out), grow only.  hipFree waits for the kernels that may still use the old one.
+int reserve_strips(pmk_model *m, int64_t slots)
+{
+    if (m->strip_slots >= slots) return 0;
+    if (m->d_strip) PMK_HIP(hipFree(m->d_strip));
+    m->d_strip = nullptr;
+    m->strip_slots = 0;
+    PMK_HIP(hipMalloc(&m->d_strip, m->esz * (size_t)((int64_t)m->max_nt * TILE * TQ * slots)));
+    m->strip_slots = slots;
+    return 0;
+}
+
 }  // namespace pmk
 
 using namespace pmk;
@@ -457,9 +470,9 @@ void pmk_model_destroy(pmk_model *m)
 {
     if (!m) return;
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
-    dev_free(m->d_order);
+    dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt);
     for (void **p : {&m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
-                     &m->d_ym, &m->d_cm}) {
+                     &m->d_ym, &m->d_cm, &m->d_loo_tasks}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -642,6 +655,8 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     m->th = *th;
     m->sigma2 = sigma2;
     m->multi_solved = false;            // a new factor: the multi-output weights are stale
+    m->loo_valid = false;               // ... and so is diag((L L^T)^-1)
+    m->loaded = false;
     int rc;
     c->tic("fit");
     // Fused kernel-matrix build (PMK_FUSE_K1=0 turns it off): for the compact Spline34 profile in 2 or 3 dimensions K1
@@ -805,6 +820,7 @@ int pmk_model_load(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const doubl
     }
     if (rc) { pmk_model_destroy(m); *out = nullptr; return rc; }
     m->fitted = true;
+    m->loaded = true;
     return 0;
 }
 
@@ -1470,6 +1486,138 @@ int pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk
         rc = pmk_query_fetch_multi(q, Yq, ldyq, Vq);
     pmk_query_destroy(q);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------ model selection
+static int evidence_common(pmk_model *m, int R, double *logdet, double *quad)
+{
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    const int cols = R ? R : 1;
+    DevTmp<double> dl, dq;
+    if ((logdet && dl.alloc(m->P)) || (quad && dq.alloc(m->P * cols))) return -100;
+    c->tic("evidence");
+    const int rc = PMK_BY_DTYPE(m, launch_evidence(m, R, dl, dq, c->stream));
+    c->toc("evidence");
+    if (rc) return rc;
+    if (logdet) PMK_HIP(hipMemcpyAsync(logdet, dl, sizeof(double) * (size_t)m->P, hipMemcpyDeviceToHost, c->stream));
+    if (quad) PMK_HIP(hipMemcpyAsync(quad, dq, sizeof(double) * (size_t)(m->P * cols), hipMemcpyDeviceToHost, c->stream));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int pmk_model_evidence(pmk_model *m, double *logdet, double *quad)
+{
+    if (!m) { set_error("pmk_model_evidence: model is NULL"); return -1; }
+    if (!m->fitted) {
+        set_error("pmk_model_evidence: no factor (run pmk_model_fit or build the model with pmk_model_load)");
+        return -2;
+    }
+    if (quad && m->loaded) {
+        set_error("pmk_model_evidence: a model built by pmk_model_load holds no targets; pass quad = NULL");
+        return -3;
+    }
+    return evidence_common(m, 0, logdet, quad);
+}
+
+int pmk_model_evidence_multi(pmk_model *m, double *logdet, double *quad)
+{
+    if (!m) { set_error("pmk_model_evidence_multi: model is NULL"); return -1; }
+    if (!m->fitted) {
+        set_error("pmk_model_evidence_multi: no factor (run pmk_model_fit or build the model with pmk_model_load)");
+        return -2;
+    }
+    if (!m->multi_solved) { set_error("pmk_model_evidence_multi: pmk_model_solve_multi has not run"); return -3; }
+    return evidence_common(m, m->R_multi, logdet, quad);
+}
+
+int pmk_model_loo(pmk_model *m)
+{
+    if (!m) { set_error("pmk_model_loo: model is NULL"); return -1; }
+    if (!m->fitted) {
+        set_error("pmk_model_loo: no factor (run pmk_model_fit or build the model with pmk_model_load)");
+        return -2;
+    }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    m->loo_valid = false;
+    c->tic("loo");
+    const int rc = PMK_BY_DTYPE(m, launch_loo(m, c->stream));
+    c->toc("loo");
+    if (rc) return rc;
+    m->loo_valid = true;
+    return 0;
+}
+
+// res (layout of the weights: tot_y x RP row-major, RP = 1 or PMK_MAX_OUTPUTS) and var (tot_y) on the host
+static int loo_values_common(pmk_model *m, int R, std::vector<double> *res, std::vector<double> *var)
+{
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    const int64_t rp = R ? PMK_MAX_OUTPUTS : 1, ny = std::max<int64_t>(m->tot_y, 1);
+    DevTmp<double> dr, dv;
+    if ((res && dr.alloc(ny * rp)) || (var && dv.alloc(ny))) return -100;
+    if (int rc = PMK_BY_DTYPE(m, launch_loo_values(m, R, dr, dv, c->stream))) return rc;
+    if (res) {
+        res->resize((size_t)(ny * rp));
+        PMK_HIP(hipMemcpyAsync(res->data(), dr, sizeof(double) * res->size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (var) {
+        var->resize((size_t)ny);
+        PMK_HIP(hipMemcpyAsync(var->data(), dv, sizeof(double) * var->size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int loo_state_ok(pmk_model *m, const char *who)
+{
+    if (!m) { set_error("%s: model is NULL", who); return -1; }
+    if (!m->fitted) { set_error("%s: no factor (run pmk_model_fit or build the model with pmk_model_load)", who); return -2; }
+    if (!m->loo_valid) { set_error("%s: pmk_model_loo has not run on the resident factor", who); return -3; }
+    return 0;
+}
+
+int pmk_model_get_loo(pmk_model *m, double *const *res, double *const *var)
+{
+    if (int rc = loo_state_ok(m, "pmk_model_get_loo")) return rc;
+    for (int64_t r = 0; r < m->P; ++r)
+        if ((res && !res[r]) || (var && !var[r])) {
+            set_error("pmk_model_get_loo: output of patch %lld is NULL", (long long)r);
+            return -4;
+        }
+    std::vector<double> hr, hv;
+    if (int rc = loo_values_common(m, 0, res ? &hr : nullptr, var ? &hv : nullptr)) return rc;
+    for (int64_t r = 0; r < m->P; ++r) {
+        const PatchDesc &d = m->desc[(size_t)r];
+        if (res) std::memcpy(res[r], hr.data() + d.yoff, sizeof(double) * (size_t)d.n);
+        if (var) std::memcpy(var[r], hv.data() + d.yoff, sizeof(double) * (size_t)d.n);
+    }
+    return 0;
+}
+
+int pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ldres, double *const *var)
+{
+    if (int rc = loo_state_ok(m, "pmk_model_get_loo_multi")) return rc;
+    if (!m->multi_solved) { set_error("pmk_model_get_loo_multi: pmk_model_solve_multi has not run"); return -3; }
+    if (RES && !ldres) { set_error("pmk_model_get_loo_multi: ldres is NULL"); return -4; }
+    for (int64_t r = 0; r < m->P; ++r)
+        if ((RES && (!RES[r] || ldres[r] < m->desc[(size_t)r].n)) || (var && !var[r])) {
+            set_error("pmk_model_get_loo_multi: bad output of patch %lld", (long long)r);
+            return -4;
+        }
+    std::vector<double> hr, hv;
+    if (int rc = loo_values_common(m, m->R_multi, RES ? &hr : nullptr, var ? &hv : nullptr)) return rc;
+    for (int64_t r = 0; r < m->P; ++r) {
+        const PatchDesc &d = m->desc[(size_t)r];
+        if (RES) {
+            const double *blk = hr.data() + d.yoff * PMK_MAX_OUTPUTS;
+            for (int j = 0; j < m->R_multi; ++j)
+                for (int64_t i = 0; i < d.n; ++i) RES[r][i + j * ldres[r]] = blk[i * PMK_MAX_OUTPUTS + j];
+        }
+        if (var) std::memcpy(var[r], hv.data() + d.yoff, sizeof(double) * (size_t)d.n);
+    }
+    return 0;
 }
 
 }  // extern "C"

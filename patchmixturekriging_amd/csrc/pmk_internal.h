@@ -125,6 +125,15 @@ struct pmk_model {
     void *d_ym = nullptr;               // targets Y
     void *d_cm = nullptr;               // weights C (the forward solve's Z in between)
     bool multi_solved = false;
+    // model selection from the resident factor (pmk_loo.hip): d = diag((L L^T)^-1), always double, yoff addressing;
+    // valid from pmk_model_loo until the next pmk_model_fit.  The strip tasks depend on the geometry only: built once.
+    double *d_dloo = nullptr;
+    bool loo_valid = false;
+    bool loaded = false;                // built by pmk_model_load: d_y holds no targets
+    void *d_loo_tasks = nullptr;        // LooTask list, grouped by queue (one queue per XCD)
+    uint32_t *d_loo_cnt = nullptr;      // 8 queue heads
+    int64_t loo_ntasks = 0;
+    int32_t loo_qoff[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 struct pmk_query {
@@ -183,6 +192,9 @@ namespace pmk {
     int launch_items(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                        \
     int launch_solve_multi(pmk_model *m, hipStream_t s);                                                             \
     int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                  \
+    int launch_loo(pmk_model *m, hipStream_t s);                                                                     \
+    int launch_evidence(const pmk_model *m, int R, double *d_logdet, double *d_quad, hipStream_t s);                 \
+    int launch_loo_values(const pmk_model *m, int R, double *d_res, double *d_var, hipStream_t s);                   \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -191,6 +203,8 @@ PMK_DECLARE_REAL_LAUNCHERS(f32)
 int launch_kernel_matrix_dense(const pmk_kernel_desc &th, int D, int64_t n, const double *d_xs, int64_t ldx,
                                int64_t mcols, const double *d_zs, int64_t ldz, double *d_K, int64_t ldk,
                                bool symmetric, hipStream_t s);
+// the strip workspace of the model (max_nt * TILE x TQ elements per slot), grow only; host side (pmk_api.cpp)
+int reserve_strips(pmk_model *m, int64_t slots);
 int set_plan_attributes();
 int launch_iota(int32_t *d, int64_t n, hipStream_t s);
 int query_reserve(pmk_query *q, int64_t Nq);

@@ -27,13 +27,6 @@
 namespace pmk {
 namespace PMK_NS {
 
-constexpr int PF_PRED = 4;          // I-operand (factor, from L2) prefetch depth in k-steps
-constexpr int PFJ_PRED = 4;         // J-operand (the wave's own strip columns, HBM) prefetch depth
-// a wave owns a 128 x 32 tile of the strip: eight waves, two per SIMD (256 registers each)
-constexpr int WCOLS = 32;           // query columns of a wave
-constexpr int PRED_WAVES = TQ / WCOLS;
-constexpr int PRED_THREADS = 64 * PRED_WAVES;
-constexpr int NC = 2;               // query columns of a lane
 constexpr int SYNC_TICKS = 4000;    // lock-step rendezvous: give up after 40 us (s_memrealtime ticks of 10 ns)
 constexpr int ROUND_TICKS = 300000; // round barrier: give up after 3 ms, and then for the rest of the launch
 
@@ -59,6 +52,26 @@ __device__ unsigned long long g_row_stamp[512 * 40];
 #define PMK_TRACED false
 #endif
 
+}  // namespace PMK_NS
+}  // namespace pmk
+
+// strip_block_row and the shape of a strip (shared with the leave-one-out kernel); in a trace build it stamps into
+// g_row_stamp above
+#ifdef PMK_TRACE
+#define PMK_STRIP_STAMPS
+#endif
+#include "pmk_strip.h"
+
+namespace pmk {
+namespace PMK_NS {
+
+// a wave owns a 128 x 32 tile of the strip: eight waves, two per SIMD (256 registers each)
+constexpr int WCOLS = 32;           // query columns of a wave
+constexpr int PRED_WAVES = TQ / WCOLS;
+constexpr int PRED_THREADS = 64 * PRED_WAVES;
+constexpr int NC = 2;               // query columns of a lane
+static_assert(WCOLS == STRIP_WCOLS && NC == STRIP_NC, "the strip shape of pmk_strip.h");
+
 struct StripTask {
     int32_t region;    // local patch index in the model
     int32_t count;     // valid columns (<= TQ)
@@ -66,27 +79,6 @@ struct StripTask {
     int32_t group;     // lock-step group (arrival counter index); -1: alone
     int32_t gsize;     // strips in the group
 };
-
-// one block row of the strip: acc = Kq_i (in) -> -V_i (out)
-template <int NACT>
-__device__ __forceinline__ void strip_block_row(WaveTile<4, 1> &acc, const real *Li, int64_t ld, const real *V, int i,
-                                                const real *Lii, const real *ninv_i, int lane, bool traced = false)
-{
-    if (i > 0) {
-        // order this wave's earlier strip stores before its loads of them
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        gemm_nt_indexed<4, 1, PF_PRED, PFJ_PRED, NACT>(acc, Li, ld, V, TQ, i * TILE, lane);
-    }
-#ifdef PMK_TRACE
-    if (traced && i == PMK_TRACE_ROW && lane == 0 && blockIdx.x < 64) {
-        g_row_stamp[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-        g_row_stamp[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + 7] = __builtin_amdgcn_s_memtime();      // shader clock
-    }
-#endif
-    // the TRSM operands come straight from the factor (prefetched block by block into registers): no LDS copy, no
-    // barrier around staging one
-    tri_solve_global<1>(acc, Lii, ld, ninv_i, lane);
-}
 
 // Kq tile of one block row (query is the first kernel argument, mixtureGP.jl:304) into the wave's accumulator, 32 rows
 // at a time in a ROLLED loop whose results pass through a lane-private LDS slot: fully unrolled, the 64 evaluations
@@ -427,14 +419,7 @@ int build_strip_tasks(pmk_query *q, hipStream_t s)
     }
     PMK_HIP(hipMemcpyAsync(q->d_tasks, tasks.data(), sizeof(StripTask) * tasks.size(), hipMemcpyHostToDevice, s));
     PMK_HIP(hipStreamSynchronize(s));        // `tasks` is a local
-    const int64_t stride = (int64_t)m->max_nt * TILE * TQ;
-    if (m->strip_slots < slots) {
-        if (m->d_strip) PMK_HIP(hipFree(m->d_strip));
-        m->d_strip = nullptr;
-        m->strip_slots = 0;
-        PMK_HIP(hipMalloc(&m->d_strip, sizeof(real) * stride * slots));
-        m->strip_slots = slots;
-    }
+    if (int rc = reserve_strips(m, slots)) return rc;
     q->strip_grid = slots;
     return 0;
 }

@@ -69,6 +69,12 @@ class DeviceModel:
         self.h = h
         self.theta = None
         self.sigma2 = None
+        # what the device model holds (mirrors the library's state rules, so that a call in the wrong state is
+        # refused before any device call)
+        self._has_factor = _factors is not None
+        self._has_targets = _factors is None
+        self._loo_done = False
+        self._multi_solved = False
 
     @classmethod
     def from_factors(cls, X_parts, c_set, L_set, ctx=None):
@@ -93,9 +99,11 @@ class DeviceModel:
         ys = [np.ascontiguousarray(y, dtype=np.float64) for y in y_parts]
         PA = _dp * self.P
         _lib.check(self.ctx.L.pmk_model_set_targets(self.h, PA(*[_d(y) for y in ys])), "pmk_model_set_targets")
+        self._has_factor = False
 
     def set_diag(self, diag_parts):
         """pmk_model_set_diag: per-point addend of the kernel's diagonal for the next fits (None clears it)"""
+        self._has_factor = False
         if diag_parts is None:
             _lib.check(self.ctx.L.pmk_model_set_diag(self.h, None), "pmk_model_set_diag")
             return
@@ -111,6 +119,8 @@ class DeviceModel:
         d = theta.desc()
         _lib.check(self.ctx.L.pmk_model_fit(self.h, C.byref(d), float(sigma2)), "pmk_model_fit")
         self.theta, self.sigma2 = theta, float(sigma2)
+        self._has_factor, self._has_targets = True, True
+        self._loo_done = self._multi_solved = False         # a new factor: d and the multi-output weights are stale
 
     def info(self):
         info = np.zeros(self.P, dtype=np.int32)
@@ -150,10 +160,12 @@ class DeviceModel:
         _lib.check(self.ctx.L.pmk_model_set_targets_multi(self.h, R, PA(*[_d(y) for y in Ys]), _i(ldy)),
                    "pmk_model_set_targets_multi")
         self.R = R
+        self._multi_solved = False
 
     def solve_multi(self):
         """pmk_model_solve_multi: C = (L L^T)^-1 Y for every column from the resident factor (no refactorisation)"""
         _lib.check(self.ctx.L.pmk_model_solve_multi(self.h), "pmk_model_solve_multi")
+        self._multi_solved = True
 
     def weights_multi(self):
         """the n_r x R weights of every patch (one device-to-host transfer)"""
@@ -166,6 +178,60 @@ class DeviceModel:
         _lib.check(self.ctx.L.pmk_model_get_weights_multi(self.h, PA(*[_d(c) for c in out]), _i(ldc)),
                    "pmk_model_get_weights_multi")
         return out
+
+    # ---- model selection from the resident factor (per patch: a point of several overlapping patches has a score in each)
+    def _need(self, factor=True, loo=False, multi=False, targets=False):
+        if factor and not self._has_factor:
+            raise _lib.PmkError("no factor: fit the model (or build it with from_factors) first")
+        if targets and not self._has_targets:
+            raise _lib.PmkError("a model built from factors holds no targets: y^T c is not available")
+        if multi and not self._multi_solved:
+            raise _lib.PmkError("solve_multi has not run on the resident factor")
+        if loo and not self._loo_done:
+            raise _lib.PmkError("loo() has not run on the resident factor")
+
+    def evidence(self, quad=True):
+        """pmk_model_evidence -> (logdet [P], quad [P] or None): log det (K + sigma2 I) = 2 sum log L_ii and y^T c of
+        every patch; NaN where the factorisation failed"""
+        self._need(targets=quad)
+        logdet, q = np.empty(self.P), (np.empty(self.P) if quad else None)
+        _lib.check(self.ctx.L.pmk_model_evidence(self.h, _d(logdet), None if q is None else _d(q)), "pmk_model_evidence")
+        return logdet, q
+
+    def evidence_multi(self):
+        """pmk_model_evidence_multi -> (logdet [P], quad [P, R]): quad[r, j] = Y_r[:, j]^T C_r[:, j]"""
+        self._need(multi=True)
+        logdet, q = np.empty(self.P), np.empty((self.P, self.R), order="F")
+        _lib.check(self.ctx.L.pmk_model_evidence_multi(self.h, _d(logdet), _d(q)), "pmk_model_evidence_multi")
+        return logdet, q
+
+    def loo(self):
+        """pmk_model_loo: d = diag((L L^T)^-1) of every patch from the resident factor (enqueues; no refit)"""
+        self._need()
+        _lib.check(self.ctx.L.pmk_model_loo(self.h), "pmk_model_loo")
+        self._loo_done = True
+
+    def loo_values(self):
+        """pmk_model_get_loo -> (res, var), one vector per patch: res_i = c_i / d_i = y_i - mu_-i (the leave-one-out
+        mean is y_i - res_i), var_i = 1 / d_i (includes sigma2)"""
+        self._need(loo=True)
+        res, var = [np.empty(int(n)) for n in self.n], [np.empty(int(n)) for n in self.n]
+        PA = _dp * self.P
+        _lib.check(self.ctx.L.pmk_model_get_loo(self.h, PA(*[_d(a) for a in res]), PA(*[_d(a) for a in var])),
+                   "pmk_model_get_loo")
+        return res, var
+
+    def loo_values_multi(self):
+        """pmk_model_get_loo_multi -> (RES, var): RES[r] is n_r x R (one residual column per target column), var is
+        shared by the columns"""
+        self._need(loo=True, multi=True)
+        RES = [np.empty((int(n), self.R), order="F") for n in self.n]
+        var = [np.empty(int(n)) for n in self.n]
+        PA = _dp * self.P
+        ld = np.array([int(n) for n in self.n], dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_get_loo_multi(self.h, PA(*[_d(a) for a in RES]), _i(ld), PA(*[_d(a) for a in var])),
+                   "pmk_model_get_loo_multi")
+        return RES, var
 
     def set_bsp(self, root, leaf_base=0):
         _lib.check(self.ctx.L.pmk_model_set_bsp(self.h, _native(root).h, int(leaf_base)), "pmk_model_set_bsp")
@@ -520,3 +586,43 @@ def querymixtureGP_multi(Xq, eta, root, levels, radius, delta, theta, sigma2, we
     q.items_multi(theta, variance)
     q.mix_multi(weight_theta)
     return q.fetch_multi(model.R)
+
+
+# ---- model selection: is this (theta, sigma2) any good on this patch?  The reference picks both by hand
+# (examples/mixGP.jl:32-35).  Both scores come from the factor that fitmixtureGP_ left on the device; they are PER PATCH
+# (overlapping eps-sets put a training point into several patches, and it has one score in each).
+def _fitted_model(eta, who):
+    if getattr(eta, "_model", None) is None:
+        raise _lib.PmkError("fitmixtureGP_ must run before %s" % who)
+    return eta._model
+
+
+def logevidencemixtureGP(eta):
+    """log marginal likelihood of every patch, -1/2 y^T c - 1/2 log det (K + sigma2 I) - n/2 log(2 pi)  -> array [P]"""
+    model = _fitted_model(eta, "logevidencemixtureGP")
+    logdet, quad = model.evidence()
+    return -0.5 * quad - 0.5 * logdet - 0.5 * model.n * np.log(2.0 * np.pi)
+
+
+def logevidencemixtureGP_multi(eta):
+    """the same for the R columns of fitmixtureGP_multi_ -> array [P, R] (one log det per patch serves every column)"""
+    model = _fitted_model(eta, "logevidencemixtureGP_multi")
+    logdet, quad = model.evidence_multi()
+    return -0.5 * quad - 0.5 * logdet[:, None] - 0.5 * model.n[:, None] * np.log(2.0 * np.pi)
+
+
+def loomixtureGP(eta):
+    """leave-one-out residuals and variances of every training point of every patch -> (res_set, var_set):
+    res_set[r][i] = y_i - mu_-i (so mu_-i = y_i - res_set[r][i]), var_set[r][i] = the predictive variance of y_i from
+    the other n_r - 1 points of patch r, noise included.  One pass over the resident factor, no refit."""
+    model = _fitted_model(eta, "loomixtureGP")
+    model.loo()
+    return model.loo_values()
+
+
+def loomixtureGP_multi(eta):
+    """the same for the R columns of fitmixtureGP_multi_ -> (RES_set [n_r x R each], var_set)"""
+    model = _fitted_model(eta, "loomixtureGP_multi")
+    model._need(multi=True)
+    model.loo()
+    return model.loo_values_multi()
