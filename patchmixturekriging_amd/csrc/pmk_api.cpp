@@ -557,6 +557,8 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
         // factorisation takes the split path (pmk_chol.hip).  The two paths sum in different orders (last-bit differences
         // in L), so the choice is kept away from everyday batches: only patches of >= 32 tiles (n > 3968) qualify, and a
         // model and its shards -- which hold the same patch sizes -- then decide alike unless they straddle P's bound.
+        // On the split path the factor's bits are a function of the patch and of max_nt (launch_cholesky: nsplit_of), so
+        // shards reproduce the single model bit for bit where their largest patch has as many tiles as the model's.
         m->split_mode = m->max_nt >= 32 && P * (int64_t)(m->max_nt - 1) / 2 < 2 * (int64_t)ctx->num_cu;
         m->active_prefix.assign((size_t)m->max_nt + 2, 0);
         for (int64_t r = 0; r < P; ++r)

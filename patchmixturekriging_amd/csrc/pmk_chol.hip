@@ -1070,10 +1070,16 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
         c->panel_n = l + 1;
         return 0;
     };
-    // split path: K chunks so that ONE patch's tiles x chunks would fill the chip (a function of the step alone, not of the
-    // number of patches: the summation order of a tile, hence every bit of the factor, is then the same whether a patch
-    // is factorised alone or next to others -- sharded and single models stay bit-identical); a chunk is at least two
-    // block columns deep; 64-way: the serial sum in the combine costs more than it buys
+    // split path: K chunks so that ONE patch's tiles x chunks would fill the chip: a function of the launch alone, not of
+    // the number of patches.  A patch of nt tiles runs its block column k at launch l = k + (max_nt - nt), so the chunks of
+    // a tile, hence its summation order and every bit of the factor, are the same whether the patch is factorised alone
+    // or next to others AS LONG AS THE BATCHES HAVE THE SAME max_nt -- a shard whose largest patch has as many tiles as
+    // the model's stays bit-identical to it.  Beside a patch with more tiles the same block column runs at a later launch
+    // with more chunks (and its first four block columns are split too): another summation order, the bits differ, and
+    // only the bound between the split and the batched path is promised (tests/test_gpu_fit_schedule.py asserts all
+    // three).  A chunk is at least two block columns deep; 64-way: the serial sum in the combine costs more than it buys.
+    // tests/_fit_schedule.py mirrors the schedule -- this function, the loop below and launch_split_solves (the tests
+    // use it to prove which branch a list of patch sizes drives): change both together.
     auto nsplit_of = [&](int l, int G) {
         return (m->split_mode && l >= 4) ? std::max(1, std::min(std::min(16, l / 2), (want_wg + G) / (G + 1))) : 1;
     };
@@ -1088,7 +1094,10 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
     if (half_tiles)
         if (int rc = reserve_split(m, 2 * sizeof(real2_t) * (size_t)PARTIAL_TILE * half_tiles, 0)) return rc;
     struct Pending { int n, G, nsplit; const real2_t *buf; int l; } pend = {0, 0, 1, nullptr, -1};
-    auto flush_pending = [&]() -> int {       // a potrf-only launch (no split step follows the one that left it)
+    // a potrf-only launch (no split step follows the one that left it).  Only the call after the loop ever finds a pending
+    // tile: nsplit_of(l, max_nt - l - 1) does not decrease with l, so no batched step follows a split one and the call
+    // inside the loop is a no-op (tests/test_fit_schedule_model.py checks max_nt <= 160, P <= 64).
+    auto flush_pending = [&]() -> int {
         if (pend.n == 0) return 0;
         hipLaunchKernelGGL(chol_partial_kernel, dim3((unsigned)pend.n), dim3(256), 0, s, m->d_desc, m->d_order, 0, 0, 1,
                            pend.l + 1, m->max_nt, (real *)m->d_a, (real2_t *)nullptr, pend.n, pend.G, pend.nsplit, pend.buf,
@@ -1143,7 +1152,7 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
 }
 
 // the two triangular solves of the split path: z = L^-1 y, then c = L^-T z, block by block with the long products cut
-// into chunks (see solve_partial_kernel)
+// into chunks (see solve_partial_kernel).  Mirrored by schedule() in tests/_fit_schedule.py.
 static int launch_split_solves(pmk_model *m, hipStream_t s)
 {
     const int P = (int)m->P;
