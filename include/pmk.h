@@ -324,6 +324,38 @@ int  pmk_model_get_loo(pmk_model *m, double *const *res, double *const *var);
 /* R columns: RES[r] is n[r] x R column-major, leading dimension ldres[r] >= n[r]; var is shared by the columns */
 int  pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ldres, double *const *var);
 
+/* ---- per-patch kernels and noise ---------------------------------------------------------------------------------------
+ * MixtureGPType carries one noise variance per patch (sigma2_set::Vector, mixtureGP.jl:44,114), and fitmixtureGP!
+ * (mixtureGP.jl:70-118) fills it with one value; here every patch may have its own kernel and its own noise variance, which
+ * is what the per-patch scores above are for.  ths[P] and sigma2[P] are indexed by the model's local patch; families may
+ * differ between patches.  The device runs the Spline34 instantiation of its kernels if EVERY patch is PMK_SPLINE34 and
+ * the run-time family switch otherwise (as the uniform calls do for one theta), so a patch's factor has the bits of the
+ * uniform fit that takes the same instantiation.  The mixture weight kernel weight_th stays global.  Not available
+ * through the sharded / all-gather exchanges (pmk_query_predict_sharded / _allgather) nor through pmk_fit_batched. */
+/* fitmixtureGP! (mixtureGP.jl:70-118) with one kernel and one noise variance PER PATCH.  The kernel matrix is always built
+ * whole (no fused build).  An unknown family in ths[r], or PMK_MODSQEXP with D > 1, returns -2 and the error text names
+ * patch r; NULL arrays return -1.  Enqueues only (after draining the stream once to replace the device copies of both
+ * arrays); the model remembers both arrays. */
+int  pmk_model_fit_patches(pmk_model *m, const pmk_kernel_desc *ths, const double *sigma2);
+/* kernels of a model built by pmk_model_load (which holds factors, mixtureGP.jl:112, but no theta), for the *_fitted
+ * calls below; -3 on any other model (a fit records its own kernels).  Blocks. */
+int  pmk_model_set_kernels(pmk_model *m, const pmk_kernel_desc *ths);
+/* the hyperparameters the resident factor belongs to: ths[P], sigma2[P] (either may be NULL).  After a plain pmk_model_fit
+ * P copies of its theta and sigma2; after pmk_model_set_kernels sigma2 is NaN (the factor's noise is not known).  -3 if
+ * the model holds no kernels. */
+int  pmk_model_get_hyper(pmk_model *m, pmk_kernel_desc *ths, double *sigma2);
+/* stage 2 (queryinner!, mixtureGP.jl:296-316) with the model's OWN kernels: region r is evaluated with the theta it was
+ * fitted with.  After a plain pmk_model_fit the same bits as pmk_query_items(q, theta).  -3 if the model holds no kernels
+ * (pmk_model_load before pmk_model_set_kernels).  Enqueues only. */
+int  pmk_query_items_fitted(pmk_query *q);
+/* pmk_query_items_multi with the model's own kernels */
+int  pmk_query_items_multi_fitted(pmk_query *q, int want_var);
+/* one-shot querymixtureGP! (mixtureGP.jl:159-294): pmk_predict_mixture / _multi without the th argument */
+int  pmk_predict_mixture_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                double radius, double delta, double *Yq, double *Vq);
+int  pmk_predict_mixture_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                      double radius, double delta, double *Yq, int64_t ldyq, double *Vq);
+
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,
                     const double *c, int64_t Nq, const double *Xq, double *Yq);

@@ -19,7 +19,8 @@ const libpmk = get(ENV, "PMK_LIB",
 export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, evalquery,
        setuppartition, getpartitionlines!, organizetrainingsets, fetchhyperplanes,
        MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
-       logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti
+       logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
+       selectmixtureGP!, selectcandidates
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -404,6 +405,7 @@ mutable struct MixtureGPType{T}           # mixtureGP.jl:38-52 (+ the device mod
     hps::Vector{HyperplaneType{T}}
     model::Ptr{Cvoid}
     handle::Ref{Ptr{Cvoid}}     # the same handle, shared with U_set / L_set
+    θ_set::Vector{Any}          # the kernel of every patch after fitmixtureGP!(η, y_parts, θs, σ²s); empty otherwise
 end
 function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{HyperplaneType{T}}) where T
     N = length(X_parts)
@@ -412,7 +414,7 @@ function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{Hyperplan
     η = MixtureGPType{T}(X_parts, Vector{Vector{T}}(undef, N), Vector{T}(undef, N),
                          LazyFactors{T,Matrix{T}}(h, 2, n, Dict{Int,Matrix{T}}()),
                          LazyFactors{T,LowerTriangular{T,Matrix{T}}}(h, 1, n, Dict{Int,LowerTriangular{T,Matrix{T}}}()),
-                         hps, C_NULL, h)
+                         hps, C_NULL, h, Any[])
     finalizer(e -> (e.model != C_NULL && ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), e.model); nothing), η)
     return η
 end
@@ -632,6 +634,158 @@ function loomixtureGPmulti(η::MixtureGPType{T}, R::Integer) where T
                                      (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
                                      η.model, [pointer(A) for A in RES], ldres, [pointer(a) for a in var]), "pmk_model_get_loo_multi")
     return [A[:, 1:R] for A in RES], var
+end
+
+# ------------------------------------------------------------------------------------------ per-patch kernels and noise
+# MixtureGPType carries one σ² per patch (σ²_set, mixtureGP.jl:44,114) and the reference fills it with one value.  Here
+# every patch may have its own θ and σ², which is what the per-patch scores above are for.  weight_θ stays global.
+# Closure-carrying kernels are refused: their warp features change the model's D, and a mix of them is not meaningful.
+perpatchok(θ) = !(θ isa WarpedKernel)
+
+"""fitmixtureGP!(η, y_parts, θs, σ²s) -> η: fitmixtureGP! (mixtureGP.jl:70-118) with θs[r], σ²s[r] for patch r
+(pmk_model_fit_patches).  Fills η.σ²_set[r] with the patch's own value and η.θ_set."""
+function fitmixtureGP!(η::MixtureGPType{T}, y_parts::Vector{Vector{T}}, θs::Vector, σ²s::Vector) where T
+    P = length(η.X_parts)
+    length(θs) == P || throw(ArgumentError("one kernel per patch: got $(length(θs)) for $P patches"))
+    length(σ²s) == P || throw(ArgumentError("one noise variance per patch: got $(length(σ²s)) for $P patches"))
+    all(perpatchok, θs) || throw(ArgumentError("closure-carrying kernels cannot be set per patch"))
+    Xm = [array2matrix(X) for X in η.X_parts]; ys = [Vector{Float64}(y) for y in y_parts]
+    n = Int64[size(x, 2) for x in Xm]; D = size(Xm[1], 1)
+    if η.model != C_NULL
+        ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), η.model)
+        η.model = C_NULL; η.handle[] = C_NULL
+    end
+    h = Ref{Ptr{Cvoid}}(C_NULL); info = Vector{Int32}(undef, P)
+    ds = KernelDesc[desc(θ) for θ in θs]; s2 = Vector{Float64}(σ²s)
+    GC.@preserve Xm ys begin
+        check(ccall((:pmk_model_create, libpmk), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}),
+            context(), D, P, n, [pointer(x) for x in Xm], [pointer(y) for y in ys], h), "pmk_model_create")
+    end
+    η.model = h[]
+    η.handle[] = h[]
+    check(ccall((:pmk_model_fit_patches, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}, Ptr{Float64}), η.model, ds, s2),
+          "pmk_model_fit_patches")
+    check(ccall((:pmk_model_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), η.model, info), "pmk_model_info")
+    empty!(η.U_set.cache); empty!(η.L_set.cache)
+    η.U_set.n = Int.(n); η.L_set.n = Int.(n)
+    bad = findfirst(!=(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))       # cholesky(U) of mixtureGP.jl:109
+    cs = [Vector{Float64}(undef, Int(n[r])) for r = 1:P]
+    GC.@preserve cs check(ccall((:pmk_model_get_weights, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), η.model,
+                                [pointer(c) for c in cs]), "pmk_model_get_weights")
+    η.θ_set = Any[θ for θ in θs]
+    for r = 1:P
+        η.c_set[r] = cs[r]
+        η.σ²_set[r] = σ²s[r]
+    end
+    return η
+end
+
+"""gethyper(η) -> (descs, σ²s): the hyperparameters the resident factor belongs to (pmk_model_get_hyper)"""
+function gethyper(η::MixtureGPType{T}) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before gethyper"))
+    P = length(η.X_parts)
+    ds = Vector{KernelDesc}(undef, P); s2 = Vector{Float64}(undef, P)
+    check(ccall((:pmk_model_get_hyper, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}, Ptr{Float64}), η.model, ds, s2),
+          "pmk_model_get_hyper")
+    return ds, s2
+end
+
+"""querymixtureGP!(Yq, Vq, Xq, η, root, levels, radius, δ, weight_θ): querymixtureGP! (mixtureGP.jl:159-294) with the
+model's own kernels, region r with the θ it was fitted with (pmk_predict_mixture_fitted).  For an η fitted per patch, or
+by the plain fitmixtureGP! with a kernel that carries no closure."""
+function querymixtureGP!(Yq::Vector{T}, Vq::Vector{T}, Xq::Vector{Vector{T}}, η::MixtureGPType{T}, root, levels,
+                         radius::T, δ::T, weight_θ)::Nothing where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before querymixtureGP!"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    resize!(Yq, Nq); resize!(Vq, Nq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    check(ccall((:pmk_predict_mixture_fitted, libpmk), Cint,
+                (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+                η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Yq, Vq), "pmk_predict_mixture_fitted")
+    return nothing
+end
+
+"""querymixtureGPmulti!(Yq, Vq, Xq, η, root, levels, radius, δ, weight_θ): the same for R target columns solved on the
+resident per-patch factor (pmk_predict_mixture_multi_fitted); Vq === nothing skips the variance."""
+function querymixtureGPmulti!(Yq::Matrix{T}, Vq::Union{Vector{T},Nothing}, Xq::Vector{Vector{T}}, η::MixtureGPType{T}, root,
+                              levels, radius::T, δ::T, weight_θ)::Nothing where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before querymixtureGPmulti!"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    size(Yq, 1) == Nq && 1 <= size(Yq, 2) <= 16 || throw(ArgumentError("Yq must be length(Xq) x R"))
+    Ym = Matrix{Float64}(undef, Nq, 16)
+    Vq === nothing || resize!(Vq, Nq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    check(ccall((:pmk_predict_mixture_multi_fitted, libpmk), Cint,
+                (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64}),
+                η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Ym, max(Nq, 1),
+                Vq === nothing ? Ptr{Float64}(C_NULL) : pointer(Vq)), "pmk_predict_mixture_multi_fitted")
+    Yq .= view(Ym, :, 1:size(Yq, 2))
+    return nothing
+end
+
+"""selectcandidates(scores) -> winners: per column (patch) of the G x P score matrix the row of the highest score; ties
+go to the lowest row, a NaN never wins, and a patch whose scores are all NaN throws, naming the patch."""
+function selectcandidates(scores::Matrix{Float64})::Vector{Int}
+    G, P = size(scores)
+    winners = Vector{Int}(undef, P)
+    for r = 1:P
+        best = 0
+        for g = 1:G
+            isnan(scores[g, r]) && continue
+            (best == 0 || scores[g, r] > scores[best, r]) && (best = g)
+        end
+        best == 0 && throw(ArgumentError("patch $r: every candidate scored NaN (no candidate could be factorised)"))
+        winners[r] = best
+    end
+    return winners
+end
+
+"""selectmixtureGP!(η, y_parts, candidates; score = :evidence) -> (η, winners, scores): `candidates` is a vector of
+(θ, σ²).  Every candidate is fitted uniformly (pmk_model_fit) and scored per patch: :evidence is the log marginal
+likelihood of logevidencemixtureGP, :loo the leave-one-out log pseudo-likelihood
+Σᵢ [-½ log varᵢ - resᵢ² / (2 varᵢ) - ½ log 2π] (Rasmussen & Williams eq. 5.10-5.11) from pmk_model_loo.  A patch whose
+factorisation fails under a candidate scores NaN for it.  selectcandidates picks the winners and one per-patch fit with
+them leaves η fitted.  Cost: G fits (plus G leave-one-out passes for :loo) plus one fit."""
+function selectmixtureGP!(η::MixtureGPType{T}, y_parts::Vector{Vector{T}}, candidates::Vector; score::Symbol = :evidence) where T
+    score in (:evidence, :loo) || throw(ArgumentError("score must be :evidence or :loo"))
+    G = length(candidates); P = length(η.X_parts)
+    G >= 1 || throw(ArgumentError("no candidates"))
+    all(c -> perpatchok(c[1]), candidates) || throw(ArgumentError("closure-carrying kernels cannot be set per patch"))
+    Xm = [array2matrix(X) for X in η.X_parts]; ys = [Vector{Float64}(y) for y in y_parts]
+    n = Int64[size(x, 2) for x in Xm]; D = size(Xm[1], 1)
+    h = Ref{Ptr{Cvoid}}(C_NULL); info = Vector{Int32}(undef, P)
+    GC.@preserve Xm ys begin
+        check(ccall((:pmk_model_create, libpmk), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}),
+            context(), D, P, n, [pointer(x) for x in Xm], [pointer(y) for y in ys], h), "pmk_model_create")
+    end
+    scores = Matrix{Float64}(undef, G, P)
+    logdet = Vector{Float64}(undef, P); quad = Vector{Float64}(undef, P)
+    res = [Vector{Float64}(undef, Int(n[r])) for r = 1:P]; var = [Vector{Float64}(undef, Int(n[r])) for r = 1:P]
+    try
+        for g = 1:G
+            θ, σ² = candidates[g]
+            check(ccall((:pmk_model_fit, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Float64), h[], Ref(desc(θ)), σ²), "pmk_model_fit")
+            check(ccall((:pmk_model_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], info), "pmk_model_info")
+            if score == :evidence
+                check(ccall((:pmk_model_evidence, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h[], logdet, quad),
+                      "pmk_model_evidence")
+                scores[g, :] = [-0.5 * quad[r] - 0.5 * logdet[r] - 0.5 * n[r] * log(2π) for r = 1:P]
+            else
+                check(ccall((:pmk_model_loo, libpmk), Cint, (Ptr{Cvoid},), h[]), "pmk_model_loo")
+                GC.@preserve res var check(ccall((:pmk_model_get_loo, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}),
+                                                 h[], [pointer(a) for a in res], [pointer(a) for a in var]), "pmk_model_get_loo")
+                scores[g, :] = [sum(-0.5 .* log.(var[r]) .- res[r] .^ 2 ./ (2 .* var[r]) .- 0.5 * log(2π)) for r = 1:P]
+            end
+        end
+    finally
+        ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), h[])
+    end
+    winners = selectcandidates(scores)
+    fitmixtureGP!(η, y_parts, Any[candidates[w][1] for w in winners], Float64[candidates[w][2] for w in winners])
+    return η, winners, scores
 end
 
 # ------------------------------------------------------------------------------------------ multi-GPU (one process per GPU)

@@ -16,7 +16,8 @@ from .kernels import (AdaptiveKernelDPPType, AdaptiveKernelMultiWarpDPPType, Ada
 from .mixture import (DeviceModel, DeviceQuery, MixtureGPDebugType, MixtureGPType,   # noqa: F401
                       PosDefException, fit_patches, fitmixtureGP_, fitmixtureGP_multi_, logevidencemixtureGP,
                       logevidencemixtureGP_multi, loomixtureGP, loomixtureGP_multi, queryinner, querymixtureGP,
-                      querymixtureGP_, querymixtureGP_multi)
+                      querymixtureGP_, querymixtureGP_multi, fitmixtureGP_patches_, querymixtureGP_patches,
+                      querymixtureGP_multi_patches, select_candidates, selectmixtureGP_)
 from .partition import (BinaryNode, HyperplaneType, PartitionDataType, array2matrix,  # noqa: F401
                         convert2itpindex, fetchhyperplanes, findneighbourpartitions, findpartition,
                         getpartitionlines_,

@@ -146,6 +146,13 @@ SIGNATURES = {
     "pmk_model_loo": (C.c_int, [_vp]),
     "pmk_model_get_loo": (C.c_int, [_vp, _dpp, _dpp]),
     "pmk_model_get_loo_multi": (C.c_int, [_vp, _dpp, _ip, _dpp]),
+    "pmk_model_fit_patches": (C.c_int, [_vp, _kp, _dp]),
+    "pmk_model_set_kernels": (C.c_int, [_vp, _kp]),
+    "pmk_model_get_hyper": (C.c_int, [_vp, _kp, _dp]),
+    "pmk_query_items_fitted": (C.c_int, [_vp]),
+    "pmk_query_items_multi_fitted": (C.c_int, [_vp, C.c_int]),
+    "pmk_predict_mixture_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp]),
+    "pmk_predict_mixture_multi_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

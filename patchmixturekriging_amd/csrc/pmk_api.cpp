@@ -1,5 +1,6 @@
 // C ABI of libpmk_hip.so (declared in include/pmk.h): contexts, models, queries.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -470,7 +471,7 @@ void pmk_model_destroy(pmk_model *m)
 {
     if (!m) return;
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
-    dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt);
+    dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt); dev_free(m->d_ths); dev_free(m->d_sigma2s);
     for (void **p : {&m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
                      &m->d_ym, &m->d_cm, &m->d_loo_tasks}) {
         if (*p) (void)hipFree(*p);
@@ -656,6 +657,10 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     pmk_ctx *c = m->ctx;
     m->th = *th;
     m->sigma2 = sigma2;
+    m->ths.assign((size_t)m->P, *th);   // the model's hyperparameters (pmk_model_get_hyper, the *_fitted calls): host only
+    m->sigma2s.assign((size_t)m->P, sigma2);
+    m->hyper_uniform = true;
+    m->hyper_s34 = th->family == PMK_SPLINE34;
     m->multi_solved = false;            // a new factor: the multi-output weights are stale
     m->loo_valid = false;               // ... and so is diag((L L^T)^-1)
     m->loaded = false;
@@ -678,6 +683,84 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     c->toc("solve");
     c->toc("fit");
     m->fitted = true;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ per-patch hyperparameters
+// ths[P] checked (family known, ModSqExp only in one dimension), remembered, and copied to the device.  The stream is
+// drained first: an earlier *_fitted launch may still be reading the device arrays.
+static int set_patch_kernels(pmk_model *m, const pmk_kernel_desc *ths, const double *sigma2, const char *who)
+{
+    for (int64_t r = 0; r < m->P; ++r) {
+        if (!kernel_ok(&ths[r])) {
+            set_error("%s: unknown kernel family %d in patch %lld", who, (int)ths[r].family, (long long)r);
+            return -2;
+        }
+        if (ths[r].family == PMK_MODSQEXP && m->D > 1) {
+            set_error("%s: patch %lld has the modulated squared-exponential kernel, which is defined for D = 1 (D = %d)", who,
+                      (long long)r, m->D);
+            return -2;
+        }
+    }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+    if (!m->d_ths && (dev_alloc(&m->d_ths, m->P) || dev_alloc(&m->d_sigma2s, m->P))) return -100;
+    m->ths.assign(ths, ths + m->P);
+    if (sigma2) m->sigma2s.assign(sigma2, sigma2 + m->P);
+    else m->sigma2s.assign((size_t)m->P, std::nan(""));        // a loaded model: the factor's noise variance is not known
+    m->hyper_uniform = false;
+    m->hyper_s34 = true;
+    for (int64_t r = 0; r < m->P; ++r) m->hyper_s34 = m->hyper_s34 && ths[r].family == PMK_SPLINE34;
+    PMK_HIP(hipMemcpy(m->d_ths, m->ths.data(), sizeof(pmk_kernel_desc) * (size_t)m->P, hipMemcpyHostToDevice));
+    PMK_HIP(hipMemcpy(m->d_sigma2s, m->sigma2s.data(), sizeof(double) * (size_t)m->P, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int pmk_model_fit_patches(pmk_model *m, const pmk_kernel_desc *ths, const double *sigma2)
+{
+    if (!m || !ths || !sigma2) { set_error("pmk_model_fit_patches: NULL argument"); return -1; }
+    pmk_ctx *c = m->ctx;
+    int rc;
+    if ((rc = set_patch_kernels(m, ths, sigma2, "pmk_model_fit_patches"))) return rc;
+    m->th = ths[0];                     // what the step launches are handed; unread without the fused build
+    m->sigma2 = sigma2[0];
+    m->multi_solved = false;            // a new factor: the multi-output weights are stale
+    m->loo_valid = false;               // ... and so is diag((L L^T)^-1)
+    m->loaded = false;
+    m->fitted = false;
+    c->tic("fit");
+    // always the whole lower triangle: the fused build evaluates tiles inside the factorisation, which knows one theta
+    m->fuse_k1 = false;
+    c->tic("kernel_matrix");
+    if ((rc = PMK_BY_DTYPE(m, launch_kernel_matrix_slabs_patches(m, c->stream, 0, m->P)))) return rc;
+    c->toc("kernel_matrix");
+    c->tic("cholesky");
+    if ((rc = PMK_BY_DTYPE(m, launch_cholesky(m, c->stream, 0, m->P)))) return rc;
+    c->toc("cholesky");
+    c->tic("solve");
+    if ((rc = PMK_BY_DTYPE(m, launch_backsolve(m, c->stream, 0, m->P)))) return rc;
+    c->toc("solve");
+    c->toc("fit");
+    m->fitted = true;
+    return 0;
+}
+
+int pmk_model_set_kernels(pmk_model *m, const pmk_kernel_desc *ths)
+{
+    if (!m || !ths) { set_error("pmk_model_set_kernels: NULL argument"); return -1; }
+    if (!m->loaded) {
+        set_error("pmk_model_set_kernels: only for a model built by pmk_model_load (a fit records its own kernels)");
+        return -3;
+    }
+    return set_patch_kernels(m, ths, nullptr, "pmk_model_set_kernels");
+}
+
+int pmk_model_get_hyper(pmk_model *m, pmk_kernel_desc *ths, double *sigma2)
+{
+    if (!m) { set_error("pmk_model_get_hyper: model is NULL"); return -1; }
+    if (m->ths.empty()) { set_error("pmk_model_get_hyper: the model holds no kernels"); return -3; }
+    if (ths) std::memcpy(ths, m->ths.data(), sizeof(pmk_kernel_desc) * (size_t)m->P);
+    if (sigma2) std::memcpy(sigma2, m->sigma2s.data(), sizeof(double) * (size_t)m->P);
     return 0;
 }
 
@@ -734,7 +817,8 @@ int pmk_model_get(pmk_model *m, int64_t patch, int what, double *out, int64_t ld
     case PMK_GET_K: {
         // U_set entry (mixtureGP.jl:99): K without noise, rebuilt on demand from the resident points
         if (ld < d.n) { set_error("pmk_model_get: ld too small"); return -5; }
-        if (!kernel_ok(&m->th)) { set_error("pmk_model_get: no kernel set (fit first)"); return -3; }
+        if (m->ths.empty()) { set_error("pmk_model_get: no kernel set (fit first)"); return -3; }
+        const pmk_kernel_desc kth = m->ths[(size_t)patch];      // the patch's own theta after pmk_model_fit_patches
         DevTmp<double> dK, dxs;
         if (dK.alloc((int64_t)d.n * d.n) || dxs.alloc((int64_t)d.ld * m->D)) return -100;
         {   // the dense host-API kernel is fp64: give it fp64 coordinates whatever the model's element type
@@ -742,7 +826,7 @@ int pmk_model_get(pmk_model *m, int64_t patch, int what, double *out, int64_t ld
             if (int rc2 = download_real_2d(m, hx.data(), d.ld, m->d_x, d.xoff, d.ld, d.ld, m->D, c->stream)) return rc2;
             PMK_HIP(hipMemcpy(dxs, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice));
         }
-        int rc = launch_kernel_matrix_dense(m->th, m->D, d.n, dxs, d.ld, d.n, dxs, d.ld, dK, d.n, true, c->stream);
+        int rc = launch_kernel_matrix_dense(kth, m->D, d.n, dxs, d.ld, d.n, dxs, d.ld, dK, d.n, true, c->stream);
         if (!rc)
             PMK_HIP(hipMemcpy2DAsync(out, sizeof(double) * ld, dK, sizeof(double) * d.n, sizeof(double) * d.n, (size_t)d.n,
                                      hipMemcpyDeviceToHost, c->stream));
@@ -1201,6 +1285,20 @@ int pmk_query_items(pmk_query *q, const pmk_kernel_desc *th)
     return rc;
 }
 
+int pmk_query_items_fitted(pmk_query *q)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_fitted: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (!m->fitted) { set_error("pmk_query_items_fitted: model is not fitted"); return -1; }
+    if (m->ths.empty()) { set_error("pmk_query_items_fitted: the model holds no kernels (pmk_model_set_kernels)"); return -3; }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    c->tic("items");
+    int rc = m->hyper_uniform ? PMK_BY_DTYPE(m, launch_items(q, m->th, c->stream)) : PMK_BY_DTYPE(m, launch_items_patches(q, c->stream));
+    c->toc("items");
+    return rc;
+}
+
 int pmk_query_item_buffers(pmk_query *q, void **u_dev, void **v_dev)
 {
     if (!q || !q->planned) { set_error("pmk_query_item_buffers: query is not planned"); return -1; }
@@ -1295,6 +1393,25 @@ int pmk_predict_mixture(pmk_model *m, const pmk_kernel_desc *th, const pmk_kerne
     return rc;
 }
 
+int pmk_predict_mixture_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq, double radius,
+                               double delta, double *Yq, double *Vq)
+{
+    if (!m) { set_error("pmk_predict_mixture_fitted: model is NULL"); return -1; }
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_predict_mixture_fitted: the model holds %lld of %lld leaves; use the staged pmk_query_* calls",
+                  (long long)m->P, (long long)m->P_global);
+        return -1;
+    }
+    pmk_query *q = nullptr;
+    int rc = pmk_query_create(m, Nq, Xq, &q);
+    if (rc) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_fitted(q)) &&
+        !(rc = pmk_query_mix(q, weight_th, 0, Nq)))
+        rc = pmk_query_fetch(q, Yq, Vq);
+    pmk_query_destroy(q);
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------ multi-output targets
 int pmk_model_set_targets_multi(pmk_model *m, int R, const double *const *Y, const int64_t *ldy)
 {
@@ -1375,10 +1492,9 @@ int pmk_model_get_weights_multi(pmk_model *m, double *const *C, const int64_t *l
     return 0;
 }
 
-int pmk_query_items_multi(pmk_query *q, const pmk_kernel_desc *th, int want_var)
+// th == NULL: the model's own per-patch kernels (pmk_query_items_multi_fitted)
+static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_var)
 {
-    if (!q || !q->planned) { set_error("pmk_query_items_multi: query is not planned"); return -1; }
-    if (!kernel_ok(th)) { set_error("pmk_query_items_multi: unknown kernel family"); return -2; }
     pmk_model *m = q->m;
     if (m->P_global != m->P || m->leaf_base != 0) {
         set_error("pmk_query_items_multi: the model holds %lld of %lld leaves; multi-output prediction needs a model that "
@@ -1414,12 +1530,28 @@ int pmk_query_items_multi(pmk_query *q, const pmk_kernel_desc *th, int want_var)
     PMK_HIP(hipMemcpyAsync(q->d_mcpre, q->mcpre.data(), sizeof(int64_t) * q->mcpre.size(), hipMemcpyHostToDevice, s));
     q->R_items = R;
     c->tic("items_multi");
-    int rc = PMK_BY_DTYPE(m, launch_items_multi(q, *th, s));
-    if (!rc && want_var) rc = PMK_BY_DTYPE(m, launch_items(q, *th, s));      // v exactly as pmk_query_items (u ignored)
+    int rc = th ? PMK_BY_DTYPE(m, launch_items_multi(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_multi_patches(q, s));
+    // v exactly as pmk_query_items / pmk_query_items_fitted (u ignored)
+    if (!rc && want_var) rc = th ? PMK_BY_DTYPE(m, launch_items(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_patches(q, s));
     c->toc("items_multi");
     if (rc) { q->R_items = 0; return rc; }
     q->var_items = want_var != 0;
     return 0;
+}
+
+int pmk_query_items_multi(pmk_query *q, const pmk_kernel_desc *th, int want_var)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_multi: query is not planned"); return -1; }
+    if (!kernel_ok(th)) { set_error("pmk_query_items_multi: unknown kernel family"); return -2; }
+    return items_multi_common(q, th, want_var);
+}
+
+int pmk_query_items_multi_fitted(pmk_query *q, int want_var)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_multi_fitted: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (m->ths.empty()) { set_error("pmk_query_items_multi_fitted: the model holds no kernels (pmk_model_set_kernels)"); return -3; }
+    return items_multi_common(q, m->hyper_uniform ? &m->th : nullptr, want_var);
 }
 
 int pmk_query_mix_multi(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1)
@@ -1484,6 +1616,26 @@ int pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk
     int rc = pmk_query_create(m, Nq, Xq, &q);
     if (rc) return rc;
     if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_multi(q, th, Vq != nullptr)) &&
+        !(rc = pmk_query_mix_multi(q, weight_th, 0, Nq)))
+        rc = pmk_query_fetch_multi(q, Yq, ldyq, Vq);
+    pmk_query_destroy(q);
+    return rc;
+}
+
+int pmk_predict_mixture_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                     double radius, double delta, double *Yq, int64_t ldyq, double *Vq)
+{
+    if (!m) { set_error("pmk_predict_mixture_multi_fitted: model is NULL"); return -1; }
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_predict_mixture_multi_fitted: the model holds %lld of %lld leaves; multi-output prediction needs a "
+                  "model that holds every leaf", (long long)m->P, (long long)m->P_global);
+        return -4;
+    }
+    if (Yq && ldyq < Nq) { set_error("pmk_predict_mixture_multi_fitted: ldyq = %lld < Nq = %lld", (long long)ldyq, (long long)Nq); return -4; }
+    pmk_query *q = nullptr;
+    int rc = pmk_query_create(m, Nq, Xq, &q);
+    if (rc) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_multi_fitted(q, Vq != nullptr)) &&
         !(rc = pmk_query_mix_multi(q, weight_th, 0, Nq)))
         rc = pmk_query_fetch_multi(q, Yq, ldyq, Vq);
     pmk_query_destroy(q);

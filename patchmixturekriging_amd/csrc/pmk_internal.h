@@ -39,6 +39,16 @@ struct PatchDesc {
     int64_t ioff;     // element offset of the negated inverted 32 x 32 diagonal blocks: nt x 4 x (32 x 32)
 };
 
+// Hyperparameter arguments of the kernels that evaluate theta (K1, the prediction strips, the multi-output means).  The
+// uniform instantiations (PP = false) take one descriptor and one noise variance by value; the per-patch ones
+// (PP = true) take the model's device arrays, indexed by the local patch.
+template <bool PP> struct HyperArgs { using th_t = pmk_kernel_desc; using s2_t = double; };
+template <> struct HyperArgs<true> {
+    // restrict: nothing the kernels write aliases the arrays, so a patch's descriptor is a scalar load into scalar registers
+    using th_t = const pmk_kernel_desc *__restrict__;
+    using s2_t = const double *__restrict__;
+};
+
 // A BSP tree in heap order (root 0, children 2i+1 / 2i+2); leaves numbered left to right.
 struct BspArrays {
     int D = 0, levels = 0;
@@ -110,6 +120,15 @@ struct pmk_model {
     bool fitted = false;
     pmk_kernel_desc th{};
     double sigma2 = 0;
+    // the hyperparameters the resident factor belongs to, per local patch.  ths is empty while the model holds no kernels
+    // (pmk_model_load before pmk_model_set_kernels).  hyper_uniform: a plain pmk_model_fit left P copies of (th, sigma2) and
+    // the *_fitted calls run the uniform kernels with m->th; otherwise they run the per-patch instantiations on the device
+    // copies below (written by pmk_model_fit_patches / pmk_model_set_kernels only).  hyper_s34: every patch is Spline34.
+    std::vector<pmk_kernel_desc> ths;
+    std::vector<double> sigma2s;
+    bool hyper_uniform = false, hyper_s34 = false;
+    pmk_kernel_desc *d_ths = nullptr;
+    double *d_sigma2s = nullptr;
     // BSP for prediction (heap order on device)
     int levels = 0;
     int64_t P_global = 0, leaf_base = 0;
@@ -193,6 +212,9 @@ namespace pmk {
     int launch_solve_multi(pmk_model *m, hipStream_t s);                                                             \
     int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                  \
     int launch_loo(pmk_model *m, hipStream_t s);                                                                     \
+    int launch_kernel_matrix_slabs_patches(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np);               \
+    int launch_items_patches(pmk_query *q, hipStream_t s);                                                           \
+    int launch_items_multi_patches(pmk_query *q, hipStream_t s);                                                     \
     int launch_evidence(const pmk_model *m, int R, double *d_logdet, double *d_quad, hipStream_t s);                 \
     int launch_loo_values(const pmk_model *m, int R, double *d_res, double *d_var, hipStream_t s);                   \
     }

@@ -15,13 +15,25 @@ namespace PMK_NS {
 // =============================================================================================
 // diag_only = false: the whole lower triangle of every patch (grid.x = its 64 x 64 tiles).  diag_only = true (fused fit):
 // only the diagonal 128 x 128 tiles (grid.x = 3 per diagonal tile of the tallest patch).
-template <int D, int FAM>
+// PP = true (pmk_model_fit_patches): theta and sigma2 of the workgroup's patch come from the model's device arrays, which
+// the host offsets by p0 like descs, so that all three are indexed by blockIdx.y.  The index is uniform over the
+// workgroup: the descriptor is a scalar load.
+template <int D, int FAM, bool PP = false>
 __global__ __launch_bounds__(256) void kmat_slab_kernel(const PatchDesc *__restrict__ descs, const real *__restrict__ x,
-                                                        real *__restrict__ A, pmk_kernel_desc th, double sigma2_d,
+                                                        real *__restrict__ A, typename HyperArgs<PP>::th_t th_arg,
+                                                        typename HyperArgs<PP>::s2_t sigma2_arg,
                                                         bool diag_only, const real *__restrict__ dg)
 {
     const PatchDesc pd = descs[blockIdx.y];
-    const real sigma2 = (real)sigma2_d;
+    pmk_kernel_desc th;
+    real sigma2;
+    if constexpr (PP) {
+        th = th_arg[blockIdx.y];
+        sigma2 = (real)sigma2_arg[blockIdx.y];
+    } else {
+        th = th_arg;
+        sigma2 = (real)sigma2_arg;
+    }
     int ti, tj;
     if (diag_only) {
         // potrf and look-ahead read the diagonal tiles from the slab; the tiles below are evaluated by the factorisation
@@ -89,6 +101,21 @@ static int launch_slab_D(const pmk_model *m, const pmk_kernel_desc &th, double s
     return 0;
 }
 
+// per-patch hyperparameters: always the whole lower triangle (the fused build evaluates tiles inside the factorisation's
+// step launches, which know one theta).  FAM = PMK_SPLINE34 if every patch is Spline34, else the run-time family switch.
+template <int D>
+static int launch_slab_patches_D(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
+{
+    const int nt64 = m->max_nt * (TILE / 64);
+    dim3 grid((unsigned)(nt64 * (nt64 + 1) / 2), (unsigned)np);
+    if (m->hyper_s34)
+        hipLaunchKernelGGL((kmat_slab_kernel<D, PMK_SPLINE34, true>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, (const pmk_kernel_desc *)(m->d_ths + p0), (const double *)(m->d_sigma2s + p0), false, (const real *)m->d_diag);
+    else
+        hipLaunchKernelGGL((kmat_slab_kernel<D, 0, true>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, (const pmk_kernel_desc *)(m->d_ths + p0), (const double *)(m->d_sigma2s + p0), false, (const real *)m->d_diag);
+    PMK_HIP(hipGetLastError());
+    return 0;
+}
+
 #define PMK_DISPATCH_D(D, CALL)                                    \
     switch (D) {                                                   \
     case 1: { constexpr int DD = 1; CALL; } break;                 \
@@ -103,6 +130,13 @@ int launch_kernel_matrix_slabs(const pmk_model *m, const pmk_kernel_desc &th, do
 {
     int rc = 0;
     PMK_DISPATCH_D(m->D, rc = launch_slab_D<DD>(m, th, sigma2, s, p0, np, diag_only));
+    return rc;
+}
+
+int launch_kernel_matrix_slabs_patches(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
+{
+    int rc = 0;
+    PMK_DISPATCH_D(m->D, rc = launch_slab_patches_D<DD>(m, s, p0, np));
     return rc;
 }
 

@@ -175,15 +175,18 @@ int launch_solve_multi(pmk_model *m, hipStream_t s)
 // -- the A operand of the MFMA, query first as in queryinner! (mixtureGP.jl:304) -- and the B operand is row k0 + (l >> 4)
 // of C_r.  Chunk g of the whole list lies in the region r with cpre[r] <= g < cpre[r + 1] (chunks per region, host
 // prefix).  Consecutive chunks share their region's C_r: xcd_remap keeps them on one XCD's L2.
+// PP = true (pmk_query_items_multi_fitted): theta of the chunk's region from the model's device array; a wave handles one
+// region, so the descriptor is wave-uniform.
 constexpr int IM_THREADS = 256;
 
-template <int D, int FAM>
+template <int D, int FAM, bool PP = false>
 __global__ __launch_bounds__(IM_THREADS) void item_means_kernel(const PatchDesc *__restrict__ descs, const real *__restrict__ x,
                                                                 const real *__restrict__ Cm, const int64_t *__restrict__ roff,
                                                                 const int64_t *__restrict__ cpre, int P, int64_t nchunks,
                                                                 const int32_t *__restrict__ sorted_item,
                                                                 const int32_t *__restrict__ item_query,
-                                                                const double *__restrict__ xq, pmk_kernel_desc th, int R,
+                                                                const double *__restrict__ xq,
+                                                                typename HyperArgs<PP>::th_t th_arg, int R,
                                                                 double *__restrict__ U)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -199,6 +202,9 @@ __global__ __launch_bounds__(IM_THREADS) void item_means_kernel(const PatchDesc 
     const int64_t first = roff[r] + (g - cpre[r]) * 16;
     const int count = (int)min((int64_t)16, roff[r + 1] - first);
     const PatchDesc pd = descs[r];
+    pmk_kernel_desc th;
+    if constexpr (PP) th = th_arg[__builtin_amdgcn_readfirstlane(r)];
+    else th = th_arg;
     const int li = lane & 15, lg = lane >> 4;
     real q[D];
     if (li < count) {
@@ -253,6 +259,33 @@ int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s)
             hipLaunchKernelGGL((item_means_kernel<DD, 0>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,                \
                                (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
                                q->d_sorted_item, q->d_item_query, q->d_xq, th, q->R_items, q->d_um);              \
+        break;
+        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
+#undef PMK_CASE
+    default:
+        set_error("prediction supports input dimension 1..4, got %d", m->D);
+        return -2;
+    }
+    PMK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_items_multi_patches(pmk_query *q, hipStream_t s)
+{
+    pmk_model *m = q->m;
+    if (q->mchunks == 0) return 0;
+    const unsigned grid = (unsigned)((q->mchunks + IM_THREADS / 64 - 1) / (IM_THREADS / 64));
+    switch (m->D) {
+#define PMK_CASE(DD)                                                                                                     \
+    case DD:                                                                                                             \
+        if (m->hyper_s34)                                                                                                \
+            hipLaunchKernelGGL((item_means_kernel<DD, PMK_SPLINE34, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc, \
+                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->R_items, q->d_um); \
+        else                                                                                                             \
+            hipLaunchKernelGGL((item_means_kernel<DD, 0, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,          \
+                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->R_items, q->d_um); \
         break;
         PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
 #undef PMK_CASE

@@ -25,6 +25,9 @@ static int no_gpu(const char *what)
     int launch_solve_multi(pmk_model *, hipStream_t) { return no_gpu("launch_solve_multi"); }                       \
     int launch_items_multi(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_items_multi"); } \
     int launch_loo(pmk_model *, hipStream_t) { return no_gpu("launch_loo"); }                                       \
+    int launch_kernel_matrix_slabs_patches(const pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_kernel_matrix_slabs_patches"); } \
+    int launch_items_patches(pmk_query *, hipStream_t) { return no_gpu("launch_items_patches"); }                   \
+    int launch_items_multi_patches(pmk_query *, hipStream_t) { return no_gpu("launch_items_multi_patches"); }       \
     int launch_evidence(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_evidence"); } \
     int launch_loo_values(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_loo_values"); } \
     }

@@ -136,7 +136,9 @@ __device__ __forceinline__ void eval_tile(WaveTile<4, 1> &acc, const real *pt, r
 //    which has the pipe anyway -- is already in its GEMM.  Both evaluations run in the shadow of the other wave's MFMAs;
 //  * the lock-step rendezvous with the other strips of the region is split-phase: thread 0 (wave 0, an early
 //    finisher) arrives for the next block row and spins, bounded, before the barrier.
-template <int D, int FAM>
+// PP = true (pmk_query_items_fitted): theta of the task's region comes from the model's device array, loaded once per
+// task; the region is uniform over the workgroup, so the descriptor stays in scalar registers.  Nothing else differs.
+template <int D, int FAM, bool PP = false>
 __global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const PatchDesc *__restrict__ descs,
                                                                const real *__restrict__ x, const real *__restrict__ A,
                                                                const real *__restrict__ inv, const real *__restrict__ cvec,
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const Pa
                                                                const int32_t *__restrict__ sorted_item,
                                                                const int32_t *__restrict__ item_query,
                                                                const double *__restrict__ xq, real *__restrict__ strips,
-                                                               int64_t strip_stride, pmk_kernel_desc th,
+                                                               int64_t strip_stride, typename HyperArgs<PP>::th_t th_arg,
                                                                uint32_t *__restrict__ sync_cnt, int round_base, double min_v,
                                                                double *__restrict__ u_out, double *__restrict__ v_out,
                                                                unsigned long long *__restrict__ clk,
@@ -195,6 +197,9 @@ __global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const Pa
         const StripTask tk = tasks[task];
         const bool active = WCOLS * wave < tk.count;     // wave-uniform
         const PatchDesc pd = descs[tk.region];
+        pmk_kernel_desc th;
+        if constexpr (PP) th = th_arg[tk.region];
+        else th = th_arg;
         const real *S = A + pd.aoff;
         const real *xs = x + pd.xoff;
         const real *cr = cvec + pd.yoff;
@@ -333,6 +338,10 @@ __global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const Pa
     }
 }
 
+// The per-patch instantiations are compiled in a translation unit of their own (pmk_predict_patches.hip includes this
+// file with PMK_PREDICT_PATCHES_TU defined): the strip kernel is the longest compile of the library, and the two halves
+// then build side by side.  This unit holds the uniform launcher and the strip tasks, that one launch_items_patches.
+#ifndef PMK_PREDICT_PATCHES_TU
 #if defined(PMK_TRACE) && !defined(PMK_REAL_F32)
 extern "C" int pmk_trace_sync_stats(unsigned long long *out, int reset)
 {
@@ -453,6 +462,41 @@ int launch_items(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s)
     PMK_HIP(hipGetLastError());
     return 0;
 }
+
+#else  // PMK_PREDICT_PATCHES_TU
+
+// the per-patch strips of pmk_query_items_fitted: theta from the model's device array.  FAM = PMK_SPLINE34 if every patch
+// is Spline34, else the run-time family switch
+int launch_items_patches(pmk_query *q, hipStream_t s)
+{
+    pmk_model *m = q->m;
+    if (q->ntasks == 0) return 0;
+    const int64_t stride = (int64_t)m->max_nt * TILE * TQ;
+    const StripTask *d_tasks = reinterpret_cast<const StripTask *>(q->d_tasks);
+    if (q->nsync > 0) PMK_HIP(hipMemsetAsync(q->d_sync, 0, sizeof(uint32_t) * (size_t)q->nsync, s));
+    switch (m->D) {
+#define PMK_CASE(DD)                                                                                                   \
+    case DD:                                                                                                           \
+        if (m->hyper_s34)                                                                                              \
+            hipLaunchKernelGGL((predict_strip_kernel<DD, PMK_SPLINE34, true>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s, \
+                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
+                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, (const pmk_kernel_desc *)m->d_ths, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
+        else                                                                                                           \
+            hipLaunchKernelGGL((predict_strip_kernel<DD, 0, true>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s,  \
+                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
+                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, (const pmk_kernel_desc *)m->d_ths, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
+        break;
+        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
+#undef PMK_CASE
+    default:
+        set_error("prediction supports input dimension 1..4, got %d", m->D);
+        return -2;
+    }
+    PMK_HIP(hipGetLastError());
+    return 0;
+}
+
+#endif  // PMK_PREDICT_PATCHES_TU
 
 }  // namespace PMK_NS
 }  // namespace pmk

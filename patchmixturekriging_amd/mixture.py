@@ -75,6 +75,7 @@ class DeviceModel:
         self._has_targets = _factors is None
         self._loo_done = False
         self._multi_solved = False
+        self._has_kernels = False       # a fit records its kernels; a model built from factors needs set_kernels
 
     @classmethod
     def from_factors(cls, X_parts, c_set, L_set, ctx=None):
@@ -120,7 +121,35 @@ class DeviceModel:
         _lib.check(self.ctx.L.pmk_model_fit(self.h, C.byref(d), float(sigma2)), "pmk_model_fit")
         self.theta, self.sigma2 = theta, float(sigma2)
         self._has_factor, self._has_targets = True, True
+        self._has_kernels = True
         self._loo_done = self._multi_solved = False         # a new factor: d and the multi-output weights are stale
+
+    def fit_patches(self, thetas, sigma2s):
+        """pmk_model_fit_patches: the fit with one kernel and one noise variance PER PATCH (thetas[r], sigma2s[r] belong
+        to patch r; families may differ).  Enqueues like fit()."""
+        descs, s2 = patch_hyper(thetas, sigma2s, self.P)
+        _lib.check(self.ctx.L.pmk_model_fit_patches(self.h, descs, _d(s2)), "pmk_model_fit_patches")
+        self.theta, self.sigma2 = None, None
+        self.thetas, self.sigma2s = list(thetas), [float(v) for v in s2]
+        self._has_factor, self._has_targets = True, True
+        self._has_kernels = True
+        self._loo_done = self._multi_solved = False
+
+    def set_kernels(self, thetas):
+        """pmk_model_set_kernels: the kernels of a model built by from_factors (which holds factors but no theta), for
+        DeviceQuery.items_fitted / items_multi_fitted"""
+        descs, _ = patch_hyper(thetas, None, self.P)
+        _lib.check(self.ctx.L.pmk_model_set_kernels(self.h, descs), "pmk_model_set_kernels")
+        self.thetas = list(thetas)
+        self._has_kernels = True
+
+    def hyper(self):
+        """pmk_model_get_hyper -> (descs, sigma2 [P]): the hyperparameters the resident factor belongs to, descs[r] =
+        (family, flags, (p0, p1, p2, p3)) of patch r.  After a plain fit() P copies of its theta and sigma2."""
+        descs = (_lib.KernelDesc * self.P)()
+        s2 = np.empty(self.P)
+        _lib.check(self.ctx.L.pmk_model_get_hyper(self.h, descs, _d(s2)), "pmk_model_get_hyper")
+        return [(int(d.family), int(d.flags), tuple(float(v) for v in d.p)) for d in descs], s2
 
     def info(self):
         info = np.zeros(self.P, dtype=np.int32)
@@ -316,6 +345,19 @@ class DeviceQuery:
         d = theta.desc()
         _lib.check(self.L.pmk_query_items(self.h, C.byref(d)), "pmk_query_items")
 
+    def items_fitted(self):
+        """pmk_query_items_fitted: stage 2 with the model's own kernels (region r with the theta it was fitted with)"""
+        if not getattr(self.model, "_has_kernels", False):
+            raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+        _lib.check(self.L.pmk_query_items_fitted(self.h), "pmk_query_items_fitted")
+
+    def items_multi_fitted(self, variance=True):
+        """pmk_query_items_multi_fitted: items_multi with the model's own kernels"""
+        if not getattr(self.model, "_has_kernels", False):
+            raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+        _lib.check(self.L.pmk_query_items_multi_fitted(self.h, int(bool(variance))), "pmk_query_items_multi_fitted")
+        self.variance = bool(variance)
+
     def item_buffers(self):
         u, v = C.c_void_p(), C.c_void_p()
         _lib.check(self.L.pmk_query_item_buffers(self.h, C.byref(u), C.byref(v)))
@@ -412,6 +454,25 @@ def multi_targets(Y_parts, n):
         if y.shape[1] != R:
             raise ValueError("patch %d: %d target columns, patch 0 has %d" % (r, y.shape[1], R))
     return Ys
+
+
+def patch_hyper(thetas, sigma2s, P):
+    """validate per-patch hyperparameters before any device call -> (pmk_kernel_desc[P], float64 [P] or None).
+    ValueError for a wrong length; TypeError for a closure-carrying kernel (anything with a diag_addend, or whose
+    kernel_points appends warp features): those change the model's D, and a mix of them is not meaningful."""
+    thetas = list(thetas)
+    if len(thetas) != P:
+        raise ValueError("one kernel per patch: got %d for %d patches" % (len(thetas), P))
+    for r, th in enumerate(thetas):
+        if hasattr(th, "diag_addend") or getattr(th, "warped", False):
+            raise TypeError("patch %d: closure-carrying kernels (%s) cannot be set per patch" % (r, type(th).__name__))
+    descs = (_lib.KernelDesc * P)(*[th.desc() for th in thetas])
+    if sigma2s is None:
+        return descs, None
+    s2 = np.ascontiguousarray(sigma2s, dtype=np.float64).reshape(-1)
+    if len(s2) != P:
+        raise ValueError("one noise variance per patch: got %d for %d patches" % (len(s2), P))
+    return descs, s2
 
 
 def fit_patches(X_parts, y_parts, theta, sigma2, ctx=None, dtype="f64"):
@@ -626,3 +687,116 @@ def loomixtureGP_multi(eta):
     model._need(multi=True)
     model.loo()
     return model.loo_values_multi()
+
+
+# ---- per-patch kernels and noise: MixtureGPType carries one sigma2 per patch (sigma2_set, mixtureGP.jl:44,114) and the
+# reference fills it with one value; here every patch may have its own theta and sigma2, which is what the per-patch
+# scores above are for.  The mixture weight kernel stays global.
+def fitmixtureGP_patches_(eta, y_parts, thetas, sigma2s):
+    """fitmixtureGP! (mixtureGP.jl:70-118) with thetas[r], sigma2s[r] for patch r -> eta.  Fills eta.sigma2_set[r] with
+    the patch's own value and eta.theta_set; raises PosDefException(patch, k) like fitmixtureGP_."""
+    patch_hyper(thetas, sigma2s, len(eta.X_parts))
+    model = DeviceModel(eta.X_parts, y_parts)
+    model.fit_patches(thetas, sigma2s)
+    info = model.info()
+    bad = np.nonzero(info)[0]
+    if len(bad):
+        raise PosDefException(int(bad[0]), int(info[bad[0]]))
+    cs = model.weights()
+    eta._model = model
+    eta.U_set._cache.clear()
+    eta.L_set._cache.clear()
+    eta.theta_set = list(thetas)
+    for r in range(len(cs)):
+        eta.c_set[r] = cs[r]
+        eta.sigma2_set[r] = float(sigma2s[r])
+    return eta
+
+
+def _patches_query(Xq, eta, root, radius, delta, who):
+    if getattr(eta, "_model", None) is None or not getattr(eta._model, "_has_kernels", False):
+        raise _lib.PmkError("fitmixtureGP_patches_ (or fitmixtureGP_) must run before %s" % who)
+    Xq = np.asarray(Xq, dtype=np.float64)
+    if Xq.ndim == 1:
+        Xq = Xq[None, :]
+    model = eta._model
+    model.set_bsp(root, 0)
+    q = DeviceQuery(model, as_points(Xq))
+    q.plan(radius, delta)
+    return q
+
+
+def querymixtureGP_patches(Xq, eta, root, levels, radius, delta, weight_theta, debug_flag=False):
+    """querymixtureGP (mixtureGP.jl:120-294) with the model's own kernels: region r is evaluated with the theta it was
+    fitted with -> (Yq, Vq, debug dict or None: DeviceQuery.debug())"""
+    q = _patches_query(Xq, eta, root, radius, delta, "querymixtureGP_patches")
+    q.items_fitted()
+    q.mix(weight_theta)
+    Yq, Vq = q.fetch()
+    return Yq, Vq, (q.debug() if debug_flag else None)
+
+
+def querymixtureGP_multi_patches(Xq, eta, root, levels, radius, delta, weight_theta, variance=True):
+    """querymixtureGP_multi with the model's own kernels, for R target columns solved on the resident per-patch factor
+    (eta._model.set_targets_multi + solve_multi) -> (Yq [Nq, R], Vq or None)"""
+    q = _patches_query(Xq, eta, root, radius, delta, "querymixtureGP_multi_patches")
+    q.model._need(multi=True)
+    q.items_multi_fitted(variance)
+    q.mix_multi(weight_theta)
+    return q.fetch_multi(q.model.R)
+
+
+def select_candidates(scores):
+    """winner per patch of a [G, P] score array (higher is better) -> int64 [P].  Ties go to the lowest candidate index,
+    a NaN never wins, and a patch whose scores are all NaN raises ValueError naming the patch."""
+    scores = np.asarray(scores, dtype=np.float64)
+    if scores.ndim != 2 or scores.shape[0] < 1:
+        raise ValueError("scores must be a [G, P] array with G >= 1")
+    winners = np.empty(scores.shape[1], dtype=np.int64)
+    for r in range(scores.shape[1]):
+        col = scores[:, r]
+        valid = np.nonzero(~np.isnan(col))[0]
+        if len(valid) == 0:
+            raise ValueError("patch %d: every candidate scored NaN (no candidate could be factorised)" % r)
+        winners[r] = valid[int(np.argmax(col[valid]))]             # argmax: the first of equal maxima
+    return winners
+
+
+def loo_log_pseudo_likelihood(res, var):
+    """sum_i [-1/2 log var_i - res_i^2 / (2 var_i) - 1/2 log 2 pi] (Rasmussen & Williams eq. 5.10-5.11) of one patch"""
+    return float(np.sum(-0.5 * np.log(var) - res * res / (2.0 * var) - 0.5 * np.log(2.0 * np.pi)))
+
+
+def selectmixtureGP_(eta, y_parts, candidates, score="evidence"):
+    """pick (theta, sigma2) per patch from `candidates`, a list of (theta, sigma2), and fit with the winners
+    -> (eta, winners [P], scores [G, P]).
+
+    Every candidate is fitted uniformly through the existing calls and scored per patch: "evidence" is the log marginal
+    likelihood as logevidencemixtureGP computes it, "loo" the leave-one-out log pseudo-likelihood from loomixtureGP's
+    residuals and variances.  A patch whose factorisation fails under a candidate scores NaN for it (no exception);
+    select_candidates picks the winners, and one fitmixtureGP_patches_ with them leaves eta fitted.
+    Cost: G fits (plus G leave-one-out passes for "loo") plus one fit."""
+    if score not in ("evidence", "loo"):
+        raise ValueError("score must be 'evidence' or 'loo'")
+    candidates = list(candidates)
+    if not candidates:
+        raise ValueError("no candidates")
+    P = len(eta.X_parts)
+    for th, _ in candidates:             # the winners go into one per-patch fit: refuse what that fit would refuse, first
+        patch_hyper([th] * P, None, P)
+    scores = np.empty((len(candidates), P))
+    model = DeviceModel(eta.X_parts, y_parts)
+    for g, (th, s2) in enumerate(candidates):
+        model.fit(th, s2)
+        model.info()                     # failed patches score NaN below: the library reports them as NaN
+        if score == "evidence":
+            logdet, quad = model.evidence()
+            scores[g] = -0.5 * quad - 0.5 * logdet - 0.5 * model.n * np.log(2.0 * np.pi)
+        else:
+            model.loo()
+            res, var = model.loo_values()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                scores[g] = [loo_log_pseudo_likelihood(a, b) for a, b in zip(res, var)]
+    winners = select_candidates(scores)
+    fitmixtureGP_patches_(eta, y_parts, [candidates[w][0] for w in winners], [candidates[w][1] for w in winners])
+    return eta, winners, scores
