@@ -356,6 +356,38 @@ int  pmk_predict_mixture_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, 
 int  pmk_predict_mixture_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                       double radius, double delta, double *Yq, int64_t ldyq, double *Vq);
 
+/* ---- device-resident set-up: a model from a tree and ONE global point array -----------------------------------------
+ * MixtureGPType(X_set, hps) after organizetrainingsets (partition.jl:301-357) or setuppartition (partition.jl:106-129)
+ * without the host lists in between: the library assigns, gathers and packs on the GPU, and keeps the index list
+ * (patch row -> global point) so that targets and the diagonal addend can be set from GLOBAL per-point arrays.  The
+ * model is the one pmk_model_create_ex builds from the host-cut sets, bit for bit, for every later call.
+ * Pointers marked "host or device" are classified by the runtime.  With a device pointer a call only enqueues on the
+ * context's stream: the caller orders the producer of that array with the context's stream, either by putting the
+ * context on the producer's stream (pmk_ctx_set_stream / pmk_ctx_set_stream_null) or by synchronising first.  With a host
+ * pointer a call returns once the array has been read. */
+/* X: host or device, point-major N x D with D = pmk_bsp_dim(bsp); y: host or device, N values, or NULL (targets zero
+ * until a *_global setter runs).  eps >= 0: patch r is the eps-set of leaf leaf_base + r (the sets of pmk_bsp_assign, in
+ * the same ascending order); eps < 0: patch r is the tree's own leaf list (needs N == pmk_bsp_num_points(bsp), else -3).
+ * The model holds the leaves [leaf_base, leaf_base + P); P == 0: all leaves from leaf_base on.  Attaches the tree (no
+ * pmk_model_set_bsp needed).  Blocks (the patch sizes come back to lay out the slabs).  -4: an empty patch (the text
+ * names the leaf); -5: N or the number of (point, leaf) pairs does not fit 31 bits. */
+int  pmk_model_create_from_bsp(pmk_ctx *ctx, const pmk_bsp *bsp, int64_t N, const double *X, const double *y, double eps,
+                               int64_t leaf_base, int64_t P, int dtype, pmk_model **out);
+/* the map from patch rows to global points: *N, offsets[P+1], inds[offsets[P]] (any pointer may be NULL); what the
+ * per-patch leave-one-out values and weights are indexed by.  Blocks if inds is given.  This and the three setters
+ * below return -3 on a model that was not made by pmk_model_create_from_bsp. */
+int  pmk_model_patch_index(pmk_model *m, int64_t *N, int64_t *offsets, int64_t *inds);
+/* pmk_model_set_targets through the index list: y holds the N targets of all points (host or device) */
+int  pmk_model_set_targets_global(pmk_model *m, const double *y);
+/* pmk_model_set_targets_multi through the index list: Y is N x R column-major with ldy >= N (host or device) */
+int  pmk_model_set_targets_multi_global(pmk_model *m, int R, const double *Y, int64_t ldy);
+/* pmk_model_set_diag through the index list: N addends (host or device); NULL clears the addend (and blocks) */
+int  pmk_model_set_diag_global(pmk_model *m, const double *diag);
+/* pmk_query_fetch / pmk_query_fetch_multi into DEVICE arrays: device-to-device copies enqueued on the context's stream,
+ * no host synchronisation.  Same argument rules as the host forms (Vq_dev must be NULL after a mean-only items_multi). */
+int  pmk_query_fetch_dev(pmk_query *q, double *Yq_dev, double *Vq_dev);
+int  pmk_query_fetch_multi_dev(pmk_query *q, double *Yq_dev, int64_t ldyq, double *Vq_dev);
+
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,
                     const double *c, int64_t Nq, const double *Xq, double *Yq);

@@ -36,6 +36,12 @@ int pmk_test_comm_force_exchange(pmk_comm *comm, int on);
  * the size; pmk_model_create picks by itself from P and the tile counts */
 int pmk_test_model_set_split(pmk_model *model, int on);
 
+/* the packed device buffers of one patch WITH their padding rows, as doubles (tests compare what the host route and the
+ * device route of the model set-up leave there): what = 0 the SoA coordinates (D rows of ld), 1 the targets (ld), 2 the
+ * diagonal addend (ld; -3 if none is set), 3 the multi-output targets (ld rows of PMK_MAX_OUTPUTS; -3 if none).  *ld
+ * receives the padded row count; out == NULL only reports it.  Blocks. */
+int pmk_test_model_packed(pmk_model *model, int64_t patch, int what, int64_t *ld, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -406,6 +406,7 @@ mutable struct MixtureGPType{T}           # mixtureGP.jl:38-52 (+ the device mod
     model::Ptr{Cvoid}
     handle::Ref{Ptr{Cvoid}}     # the same handle, shared with U_set / L_set
     Î¸_set::Vector{Any}          # the kernel of every patch after fitmixtureGP!(Î·, y_parts, Î¸s, ÏƒÂ²s); empty otherwise
+    N_global::Int               # > 0: built by MixtureGPType(root, X, Îµ) from N_global points; the model is resident
 end
 function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{HyperplaneType{T}}) where T
     N = length(X_parts)
@@ -414,8 +415,55 @@ function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{Hyperplan
     Î· = MixtureGPType{T}(X_parts, Vector{Vector{T}}(undef, N), Vector{T}(undef, N),
                          LazyFactors{T,Matrix{T}}(h, 2, n, Dict{Int,Matrix{T}}()),
                          LazyFactors{T,LowerTriangular{T,Matrix{T}}}(h, 1, n, Dict{Int,LowerTriangular{T,Matrix{T}}}()),
-                         hps, C_NULL, h, Any[])
+                         hps, C_NULL, h, Any[], 0)
     finalizer(e -> (e.model != C_NULL && ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), e.model); nothing), Î·)
+    return Î·
+end
+
+"""MixtureGPType(root, X, Îµ) -> Î·: the patches of the tree `root` from ONE global point matrix X (D x N), assigned, gathered
+and packed on the device (pmk_model_create_from_bsp).  Îµ >= 0: the Îµ-sets of organizetrainingsets; Îµ < 0: the tree's own
+leaves (setuppartition; X must be the matrix the tree was built on).  The tree is attached and the model stays resident:
+fitmixtureGP!(Î·, y::Vector, Î¸, ÏƒÂ²) takes the targets of all N points.  Kernels that carry a closure are refused there:
+their points carry more coordinates than the tree."""
+function MixtureGPType(root, X::Matrix{Float64}, Îµ::Real)
+    N = size(X, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_model_create_from_bsp, libpmk), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+        context(), native(root), N, X, C_NULL, Float64(Îµ), 0, 0, 0, h), "pmk_model_create_from_bsp")
+    P = Int(ccall((:pmk_model_num_patches, libpmk), Int64, (Ptr{Cvoid},), h[]))
+    off = Vector{Int64}(undef, P + 1)
+    check(ccall((:pmk_model_patch_index, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h[], C_NULL, off, C_NULL),
+          "pmk_model_patch_index")
+    inds = Vector{Int64}(undef, max(off[end], 1))
+    check(ccall((:pmk_model_patch_index, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h[], C_NULL, C_NULL, inds),
+          "pmk_model_patch_index")
+    X_parts = [[X[:, inds[k] + 1] for k = off[r] + 1:off[r + 1]] for r = 1:P]
+    Î· = MixtureGPType(X_parts, fetchhyperplanes(root))
+    Î·.model = h[]; Î·.handle[] = h[]; Î·.N_global = N
+    return Î·
+end
+
+"""fitmixtureGP!(Î·, y, Î¸, ÏƒÂ²) -> Î· on an Î· built by MixtureGPType(root, X, Îµ): y holds the targets of all N points; the
+resident model gets them through its index list (pmk_model_set_targets_global) and is refitted.  No model is created."""
+function fitmixtureGP!(Î·::MixtureGPType{Float64}, y::Vector{Float64}, Î¸, ÏƒÂ²)
+    Î·.N_global > 0 || throw(ArgumentError("this Î· was built from lists of patches: pass y_parts, one vector per patch"))
+    length(y) == Î·.N_global || throw(ArgumentError("one target per point: got $(length(y)) for $(Î·.N_global) points"))
+    perpatchok(Î¸) || throw(ArgumentError("closure-carrying kernels are not available on an Î· built from a tree and global points"))
+    P = length(Î·.X_parts); info = Vector{Int32}(undef, P)
+    check(ccall((:pmk_model_set_targets_global, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}), Î·.model, y), "pmk_model_set_targets_global")
+    check(ccall((:pmk_model_fit, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Float64), Î·.model, Ref(desc(Î¸)), ÏƒÂ²), "pmk_model_fit")
+    check(ccall((:pmk_model_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), Î·.model, info), "pmk_model_info")
+    empty!(Î·.U_set.cache); empty!(Î·.L_set.cache)
+    bad = findfirst(!=(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))       # cholesky(U) of mixtureGP.jl:109
+    cs = [Vector{Float64}(undef, length(Î·.X_parts[r])) for r = 1:P]
+    GC.@preserve cs check(ccall((:pmk_model_get_weights, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), Î·.model,
+                                [pointer(c) for c in cs]), "pmk_model_get_weights")
+    for r = 1:P
+        Î·.c_set[r] = cs[r]
+        Î·.ÏƒÂ²_set[r] = ÏƒÂ²
+    end
     return Î·
 end
 
@@ -438,7 +486,7 @@ function fitmixtureGP!(Î·::MixtureGPType{T}, y_parts::Vector{Vector{T}}, Î¸, ÏƒÂ
     end
     if Î·.model != C_NULL
         ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), Î·.model)
-        Î·.model = C_NULL; Î·.handle[] = C_NULL
+        Î·.model = C_NULL; Î·.handle[] = C_NULL; Î·.N_global = 0
     end
     h = Ref{Ptr{Cvoid}}(C_NULL); info = Vector{Int32}(undef, P); d = Ref(desc(Î¸))
     gs = [diagaddend(Î¸, X) for X in Î·.X_parts]          # the DPP kernels' own diagonal term, else nothing
@@ -653,7 +701,7 @@ function fitmixtureGP!(Î·::MixtureGPType{T}, y_parts::Vector{Vector{T}}, Î¸s::Ve
     n = Int64[size(x, 2) for x in Xm]; D = size(Xm[1], 1)
     if Î·.model != C_NULL
         ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), Î·.model)
-        Î·.model = C_NULL; Î·.handle[] = C_NULL
+        Î·.model = C_NULL; Î·.handle[] = C_NULL; Î·.N_global = 0
     end
     h = Ref{Ptr{Cvoid}}(C_NULL); info = Vector{Int32}(undef, P)
     ds = KernelDesc[desc(Î¸) for Î¸ in Î¸s]; s2 = Vector{Float64}(ÏƒÂ²s)

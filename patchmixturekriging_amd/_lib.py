@@ -153,12 +153,21 @@ SIGNATURES = {
     "pmk_query_items_multi_fitted": (C.c_int, [_vp, C.c_int]),
     "pmk_predict_mixture_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp]),
     "pmk_predict_mixture_multi_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp]),
+    "pmk_model_create_from_bsp": (C.c_int, [_vp, _vp, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64,
+                                            C.c_int, _vpp]),
+    "pmk_model_patch_index": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "pmk_model_set_targets_global": (C.c_int, [_vp, C.c_void_p]),
+    "pmk_model_set_targets_multi_global": (C.c_int, [_vp, C.c_int, C.c_void_p, C.c_int64]),
+    "pmk_model_set_diag_global": (C.c_int, [_vp, C.c_void_p]),
+    "pmk_query_fetch_dev": (C.c_int, [_vp, C.c_void_p, C.c_void_p]),
+    "pmk_query_fetch_multi_dev": (C.c_int, [_vp, C.c_void_p, C.c_int64, C.c_void_p]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "pmk_selftest_mfma_peak": (C.c_int, [_vp, _dp]),
     "pmk_test_comm_force_exchange": (C.c_int, [_vp, C.c_int]),
     "pmk_test_model_set_split": (C.c_int, [_vp, C.c_int]),
+    "pmk_test_model_packed": (C.c_int, [_vp, C.c_int64, C.c_int, _ip, _dp]),
 }
 
 

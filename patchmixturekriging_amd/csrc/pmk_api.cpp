@@ -26,6 +26,8 @@ int bsp_from_hyperplanes(int D, int levels, const double *hp_v, const double *hp
 int bsp_build_device(pmk_ctx *c, int D, int64_t N, const double *X, int levels, int sign_mode, int dot_mode, BspArrays &t);
 int bsp_assign_device(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets,
                       int64_t *inds, int64_t *list_offsets, int64_t *lists);
+int bsp_patch_index_device(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets,
+                           int32_t **d_inds, double **d_X);
 int64_t bsp_find(const BspArrays &t, const double *x);
 int bsp_assign(const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets, int64_t *inds,
                int64_t *list_offsets, int64_t *lists);
@@ -472,6 +474,7 @@ void pmk_model_destroy(pmk_model *m)
     if (!m) return;
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
     dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt); dev_free(m->d_ths); dev_free(m->d_sigma2s);
+    dev_free(m->d_pidx_off); dev_free(m->d_pidx); dev_free(m->d_gchunk); dev_free(m->d_gstage);
     for (void **p : {&m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
                      &m->d_ym, &m->d_cm, &m->d_loo_tasks}) {
         if (*p) (void)hipFree(*p);
@@ -496,16 +499,13 @@ int pmk_model_create(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const dou
     return pmk_model_create_ex(ctx, D, P, n, X, y, PMK_F64, out);
 }
 
-int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const double *const *X,
-                        const double *const *y, int dtype, pmk_model **out)
+// The geometry of a model from its patch sizes, shared by every way of creating one (host lists: pmk_model_create_ex;
+// tree + global points: pmk_model_create_from_bsp): the PatchDesc layout, the device buffers, the factorisation order
+// and the split-path rule.  `first_leaf` only numbers the patch in the error text of an empty one.  The buffers come back
+// allocated and empty; d_desc, d_order and the zeroed d_info are on the device.
+static int model_geometry(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, int dtype, const char *who, int64_t first_leaf,
+                          pmk_model **out)
 {
-    if (!out) { set_error("pmk_model_create: out is NULL"); return -7; }
-    *out = nullptr;
-    if (dtype != PMK_F64 && dtype != PMK_F32) { set_error("pmk_model_create: unknown dtype %d", dtype); return -8; }
-    if (!ctx) { set_error("pmk_model_create: ctx is NULL"); return -1; }
-    if (D < 1 || D > MAX_D) { set_error("pmk_model_create: D=%d outside 1..%d", D, MAX_D); return -2; }
-    if (P < 1 || !n || !X || !y) { set_error("pmk_model_create: no patches"); return -3; }
-    PMK_HIP(hipSetDevice(ctx->device));
     pmk_model *m = new (std::nothrow) pmk_model();
     if (!m) { set_error("out of memory"); return -100; }
     m->ctx = ctx; m->D = D; m->P = P;
@@ -513,8 +513,8 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
     m->desc.resize((size_t)P);
     int64_t a = 0, xo = 0, yo = 0, io = 0;
     for (int64_t r = 0; r < P; ++r) {
-        if (n[r] < 1 || n[r] > (1 << 24) || !X[r]) {
-            set_error("pmk_model_create: patch %lld has n=%lld (the reference asserts a non-empty patch)", (long long)r,
+        if (n[r] < 1 || n[r] > (1 << 24)) {
+            set_error("%s: patch %lld has n=%lld (the reference asserts a non-empty patch)", who, (long long)(first_leaf + r),
                       (long long)n[r]);
             delete m;
             return -4;
@@ -547,37 +547,61 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
     rc |= dev_alloc(&m->d_info, P);
     rc |= dev_alloc(&m->d_order, P);
     if (rc) { pmk_model_destroy(m); return -100; }
-    {
-        // factorisation order: by tile count, largest first (stable, so equal sizes keep the caller's order)
-        std::vector<int32_t> order((size_t)P);
-        for (int64_t r = 0; r < P; ++r) order[(size_t)r] = (int32_t)r;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int32_t a2, int32_t b2) { return m->desc[(size_t)a2].nt > m->desc[(size_t)b2].nt; });
-        // one workgroup per block row fills the chip only if there are enough patches: P (max_nt - 1) / 2 block rows per
-        // step on average against two workgroups per CU.  Below that -- single large problems, fitRKHS! at scale -- the
-        // factorisation takes the split path (pmk_chol.hip).  The two paths sum in different orders (last-bit differences
-        // in L), so the choice is kept away from everyday batches: only patches of >= 32 tiles (n > 3968) qualify, and a
-        // model and its shards -- which hold the same patch sizes -- then decide alike unless they straddle P's bound.
-        // On the split path the factor's bits are a function of the patch and of max_nt (launch_cholesky: nsplit_of), so
-        // shards reproduce the single model bit for bit where their largest patch has as many tiles as the model's.
-        m->split_mode = m->max_nt >= 32 && P * (int64_t)(m->max_nt - 1) / 2 < 2 * (int64_t)ctx->num_cu;
-        m->active_prefix.assign((size_t)m->max_nt + 2, 0);
-        for (int64_t r = 0; r < P; ++r)
-            for (int t = 0; t <= m->desc[(size_t)r].nt; ++t) ++m->active_prefix[(size_t)t];
-        if (hipMemcpy(m->d_order, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("pmk_model_create: upload failed");
-            pmk_model_destroy(m);
-            return -100;
+    // factorisation order: by tile count, largest first (stable, so equal sizes keep the caller's order)
+    std::vector<int32_t> order((size_t)P);
+    for (int64_t r = 0; r < P; ++r) order[(size_t)r] = (int32_t)r;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t a2, int32_t b2) { return m->desc[(size_t)a2].nt > m->desc[(size_t)b2].nt; });
+    // one workgroup per block row fills the chip only if there are enough patches: P (max_nt - 1) / 2 block rows per
+    // step on average against two workgroups per CU.  Below that -- single large problems, fitRKHS! at scale -- the
+    // factorisation takes the split path (pmk_chol.hip).  The two paths sum in different orders (last-bit differences
+    // in L), so the choice is kept away from everyday batches: only patches of >= 32 tiles (n > 3968) qualify, and a
+    // model and its shards -- which hold the same patch sizes -- then decide alike unless they straddle P's bound.
+    // On the split path the factor's bits are a function of the patch and of max_nt (launch_cholesky: nsplit_of), so
+    // shards reproduce the single model bit for bit where their largest patch has as many tiles as the model's.
+    m->split_mode = m->max_nt >= 32 && P * (int64_t)(m->max_nt - 1) / 2 < 2 * (int64_t)ctx->num_cu;
+    m->active_prefix.assign((size_t)m->max_nt + 2, 0);
+    for (int64_t r = 0; r < P; ++r)
+        for (int t = 0; t <= m->desc[(size_t)r].nt; ++t) ++m->active_prefix[(size_t)t];
+    // d_info on the context's (non-blocking) stream: a null-stream memset would not be ordered with the fit that follows
+    if (hipMemcpy(m->d_order, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->d_desc, m->desc.data(), sizeof(PatchDesc) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemsetAsync(m->d_info, 0, sizeof(int32_t) * (size_t)P, ctx->stream) != hipSuccess) {
+        set_error("%s: upload failed", who);
+        pmk_model_destroy(m);
+        return -100;
+    }
+    *out = m;
+    return 0;
+}
+
+int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const double *const *X,
+                        const double *const *y, int dtype, pmk_model **out)
+{
+    if (!out) { set_error("pmk_model_create: out is NULL"); return -7; }
+    *out = nullptr;
+    if (dtype != PMK_F64 && dtype != PMK_F32) { set_error("pmk_model_create: unknown dtype %d", dtype); return -8; }
+    if (!ctx) { set_error("pmk_model_create: ctx is NULL"); return -1; }
+    if (D < 1 || D > MAX_D) { set_error("pmk_model_create: D=%d outside 1..%d", D, MAX_D); return -2; }
+    if (P < 1 || !n || !X || !y) { set_error("pmk_model_create: no patches"); return -3; }
+    PMK_HIP(hipSetDevice(ctx->device));
+    for (int64_t r = 0; r < P; ++r) {
+        if (n[r] < 1 || n[r] > (1 << 24) || !X[r]) {
+            set_error("pmk_model_create: patch %lld has n=%lld (the reference asserts a non-empty patch)", (long long)r,
+                      (long long)n[r]);
+            return -4;
         }
     }
+    pmk_model *m = nullptr;
+    int rc = model_geometry(ctx, D, P, n, dtype, "pmk_model_create", 0, &m);
+    if (rc) return rc;
     {
-        std::vector<double> hx((size_t)xo);
+        std::vector<double> hx((size_t)m->tot_x);
         for (int64_t r = 0; r < P; ++r) {
             const PatchDesc &d = m->desc[(size_t)r];
             pack_soa(D, d.n, d.ld, X[r], hx.data() + d.xoff);
         }
-        if (upload_real(m, m->d_x, 0, hx.data(), hx.size()) ||
-            hipMemcpy(m->d_desc, m->desc.data(), sizeof(PatchDesc) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess) {
+        if (upload_real(m, m->d_x, 0, hx.data(), hx.size())) {
             set_error("pmk_model_create: upload failed");
             pmk_model_destroy(m);
             return -100;
@@ -585,13 +609,181 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
     }
     rc = upload_targets(m, y);
     if (rc) { pmk_model_destroy(m); return rc; }
-    // on the context's (non-blocking) stream: a null-stream memset would not be ordered with the fit that follows
-    if (hipMemsetAsync(m->d_info, 0, sizeof(int32_t) * (size_t)P, ctx->stream) != hipSuccess) {
-        set_error("pmk_model_create: memset failed");
+    *out = m;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ tree + global points
+// true if p is device memory (what the gather kernels can read); a plain or pinned host array is staged first
+static bool is_device_pointer(const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                 // an unregistered host pointer: not an error of ours
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
+// a global array of `count` doubles where the gather kernels can read it: the caller's device pointer as it is (nothing
+// waits), or a copy in the model's staging buffer (returns once the host array has been read)
+static int global_source(pmk_model *m, const double *src, size_t count, const double **d_src)
+{
+    hipStream_t s = m->ctx->stream;
+    if (is_device_pointer(src)) { *d_src = src; return 0; }
+    const size_t bytes = sizeof(double) * std::max<size_t>(count, 1);
+    if (m->gstage_bytes < bytes) {
+        PMK_HIP(hipStreamSynchronize(s));        // an earlier gather may still read the old one
+        dev_free(m->d_gstage);
+        m->gstage_bytes = 0;
+        PMK_HIP(hipMalloc((void **)&m->d_gstage, bytes));
+        m->gstage_bytes = bytes;
+    }
+    PMK_HIP(hipMemcpyAsync(m->d_gstage, src, sizeof(double) * count, hipMemcpyHostToDevice, s));
+    PMK_HIP(hipStreamSynchronize(s));
+    *d_src = m->d_gstage;
+    return 0;
+}
+
+int pmk_model_create_from_bsp(pmk_ctx *ctx, const pmk_bsp *bsp, int64_t N, const double *X, const double *y, double eps,
+                              int64_t leaf_base, int64_t P, int dtype, pmk_model **out)
+{
+    if (!out) { set_error("pmk_model_create_from_bsp: out is NULL"); return -7; }
+    *out = nullptr;
+    if (dtype != PMK_F64 && dtype != PMK_F32) { set_error("pmk_model_create_from_bsp: unknown dtype %d", dtype); return -8; }
+    if (!ctx || !bsp || !X) { set_error("pmk_model_create_from_bsp: NULL argument"); return -1; }
+    const BspArrays &t = bsp->t;
+    if (t.D < 1 || t.D > MAX_D) { set_error("pmk_model_create_from_bsp: D=%d outside 1..%d", t.D, MAX_D); return -2; }
+    if (N < 1) { set_error("pmk_model_create_from_bsp: no points"); return -3; }
+    if (N >= 0x7fffffff) { set_error("pmk_model_create_from_bsp: N must be below 2^31-1"); return -5; }
+    if (!(eps >= 0) && N != t.N) {
+        set_error("pmk_model_create_from_bsp: the tree's own leaves hold %lld points, N = %lld", (long long)t.N, (long long)N);
+        return -3;
+    }
+    if (P == 0) P = t.P - leaf_base;
+    if (leaf_base < 0 || P < 1 || leaf_base + P > t.P) {
+        set_error("pmk_model_create_from_bsp: leaves [%lld, %lld) outside the tree's %lld leaves", (long long)leaf_base,
+                  (long long)(leaf_base + P), (long long)t.P);
+        return -3;
+    }
+    PMK_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> off((size_t)t.P + 1);
+    DevTmp<int32_t> d_all;                       // the index list of ALL leaves
+    DevTmp<double> d_X;
+    int rc = bsp_patch_index_device(ctx, t, N, X, eps >= 0 ? eps : -1.0, off.data(), &d_all.p, &d_X.p);
+    if (rc) return rc;
+    std::vector<int64_t> n((size_t)P);
+    for (int64_t r = 0; r < P; ++r) n[(size_t)r] = off[(size_t)(leaf_base + r + 1)] - off[(size_t)(leaf_base + r)];
+    pmk_model *m = nullptr;
+    rc = model_geometry(ctx, t.D, P, n.data(), dtype, "pmk_model_create_from_bsp", leaf_base, &m);
+    if (rc) return rc;
+    // the model's own index list: the leaves [leaf_base, leaf_base + P) of the sorted list, offsets from 0
+    m->from_bsp = true;
+    m->N_global = N;
+    m->pidx_off.resize((size_t)P + 1);
+    std::vector<int32_t> chunk((size_t)P + 1, 0);
+    for (int64_t r = 0; r <= P; ++r) m->pidx_off[(size_t)r] = off[(size_t)(leaf_base + r)] - off[(size_t)leaf_base];
+    for (int64_t r = 0; r < P; ++r) chunk[(size_t)r + 1] = chunk[(size_t)r] + (m->desc[(size_t)r].ld + 255) / 256;
+    m->gchunks = chunk[(size_t)P];
+    const int64_t total = m->pidx_off[(size_t)P];
+    hipStream_t s = ctx->stream;
+    const double *d_y = nullptr;
+    if (dev_alloc(&m->d_pidx, total) || dev_alloc(&m->d_pidx_off, P + 1) || dev_alloc(&m->d_gchunk, P + 1) ||
+        (y && global_source(m, y, (size_t)N, &d_y)) ||
+        hipMemcpyAsync(m->d_pidx, d_all.p + off[(size_t)leaf_base], sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(m->d_pidx_off, m->pidx_off.data(), sizeof(int64_t) * (size_t)(P + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(m->d_gchunk, chunk.data(), sizeof(int32_t) * (size_t)(P + 1), hipMemcpyHostToDevice, s) != hipSuccess) {
+        set_error("pmk_model_create_from_bsp: upload failed");
         pmk_model_destroy(m);
         return -100;
     }
+    rc = PMK_BY_DTYPE(m, launch_gather_points(m, d_X.p, d_y, s));
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) { set_error("pmk_model_create_from_bsp: gather failed"); rc = -100; }
+    if (!rc) rc = pmk_model_set_bsp(m, bsp, leaf_base);
+    if (rc) { pmk_model_destroy(m); return rc; }
     *out = m;
+    return 0;
+}
+
+int pmk_model_patch_index(pmk_model *m, int64_t *N, int64_t *offsets, int64_t *inds)
+{
+    if (!m) { set_error("pmk_model_patch_index: model is NULL"); return -1; }
+    if (!m->from_bsp) { set_error("pmk_model_patch_index: the model was not made by pmk_model_create_from_bsp"); return -3; }
+    if (N) *N = m->N_global;
+    if (offsets) std::copy(m->pidx_off.begin(), m->pidx_off.end(), offsets);
+    if (inds) {
+        const int64_t total = m->pidx_off[(size_t)m->P];
+        std::vector<int32_t> h32((size_t)total);
+        PMK_HIP(hipSetDevice(m->ctx->device));
+        PMK_HIP(hipMemcpyAsync(h32.data(), m->d_pidx, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, m->ctx->stream));
+        PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+        for (int64_t i = 0; i < total; ++i) inds[i] = h32[(size_t)i];
+    }
+    return 0;
+}
+
+int pmk_model_set_targets_global(pmk_model *m, const double *y)
+{
+    if (!m || !y) { set_error("pmk_model_set_targets_global: NULL argument"); return -1; }
+    if (!m->from_bsp) { set_error("pmk_model_set_targets_global: the model was not made by pmk_model_create_from_bsp"); return -3; }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    m->fitted = false;
+    const double *d_src = nullptr;
+    if (int rc = global_source(m, y, (size_t)m->N_global, &d_src)) return rc;
+    return PMK_BY_DTYPE(m, launch_gather_vector(m, d_src, m->d_y, m->ctx->stream));
+}
+
+int pmk_model_set_diag_global(pmk_model *m, const double *diag)
+{
+    if (!m) { set_error("pmk_model_set_diag_global: model is NULL"); return -1; }
+    if (!m->from_bsp) { set_error("pmk_model_set_diag_global: the model was not made by pmk_model_create_from_bsp"); return -3; }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    m->fitted = false;
+    if (!diag) {
+        // the buffer may still be read by an enqueued fit: drain the stream before it goes (the one blocking case)
+        PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+        if (m->d_diag) (void)hipFree(m->d_diag);
+        m->d_diag = nullptr;
+        return 0;
+    }
+    if (!m->d_diag && hipMalloc(&m->d_diag, m->esz * (size_t)std::max<int64_t>(m->tot_y, 1)) != hipSuccess) {
+        set_error("pmk_model_set_diag_global: out of device memory");
+        return -100;
+    }
+    const double *d_src = nullptr;
+    if (int rc = global_source(m, diag, (size_t)m->N_global, &d_src)) return rc;
+    return PMK_BY_DTYPE(m, launch_gather_vector(m, d_src, m->d_diag, m->ctx->stream));
+}
+
+int pmk_model_set_targets_multi_global(pmk_model *m, int R, const double *Y, int64_t ldy)
+{
+    if (!m || !Y) { set_error("pmk_model_set_targets_multi_global: NULL argument"); return -1; }
+    if (!m->from_bsp) {
+        set_error("pmk_model_set_targets_multi_global: the model was not made by pmk_model_create_from_bsp");
+        return -3;
+    }
+    if (R < 1 || R > PMK_MAX_OUTPUTS) {
+        set_error("pmk_model_set_targets_multi_global: R=%d outside 1..%d", R, PMK_MAX_OUTPUTS);
+        return -2;
+    }
+    if (ldy < m->N_global) {
+        set_error("pmk_model_set_targets_multi_global: ldy = %lld < N = %lld", (long long)ldy, (long long)m->N_global);
+        return -3;
+    }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    const size_t count = (size_t)m->tot_y * PMK_MAX_OUTPUTS;
+    if (!m->d_ym) {
+        if (hipMalloc(&m->d_ym, m->esz * count) != hipSuccess || hipMalloc(&m->d_cm, m->esz * count) != hipSuccess) {
+            set_error("pmk_model_set_targets_multi_global: out of device memory");
+            return -100;
+        }
+    }
+    m->R_multi = 0;
+    m->multi_solved = false;
+    const double *d_src = nullptr;
+    if (int rc = global_source(m, Y, (size_t)(ldy * (R - 1) + m->N_global), &d_src)) return rc;
+    if (int rc = PMK_BY_DTYPE(m, launch_gather_multi(m, R, d_src, ldy, m->ctx->stream))) return rc;
+    m->R_multi = R;
     return 0;
 }
 
@@ -647,6 +839,22 @@ int pmk_test_model_set_split(pmk_model *m, int on)
     m->split_mode = on != 0 && m->max_nt >= 2;
     m->chain_mode = on == 2 ? 0 : on == 3 ? 1 : -1;
     return 0;
+}
+
+/* include/pmk_test.h: the packed buffers of one patch, padding rows included */
+int pmk_test_model_packed(pmk_model *m, int64_t patch, int what, int64_t *ld, double *out)
+{
+    if (!m || patch < 0 || patch >= m->P) { set_error("pmk_test_model_packed: bad model or patch"); return -1; }
+    const PatchDesc &d = m->desc[(size_t)patch];
+    if (ld) *ld = d.ld;
+    const void *src = what == 0 ? m->d_x : what == 1 ? m->d_y : what == 2 ? m->d_diag : what == 3 ? m->d_ym : nullptr;
+    if (what < 0 || what > 3) { set_error("pmk_test_model_packed: unknown buffer %d", what); return -2; }
+    if (!src || (what == 3 && m->R_multi < 1)) { set_error("pmk_test_model_packed: the buffer is not set"); return -3; }
+    if (!out) return 0;
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    const int64_t off = what == 0 ? d.xoff : what == 3 ? d.yoff * PMK_MAX_OUTPUTS : d.yoff;
+    const int64_t count = (int64_t)d.ld * (what == 0 ? m->D : what == 3 ? PMK_MAX_OUTPUTS : 1);
+    return download_real_2d(m, out, count, src, off, count, count, 1, m->ctx->stream);
 }
 
 int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
@@ -1336,6 +1544,18 @@ int pmk_query_fetch(pmk_query *q, double *Yq, double *Vq)
     return 0;
 }
 
+int pmk_query_fetch_dev(pmk_query *q, double *Yq_dev, double *Vq_dev)
+{
+    if (!q) { set_error("pmk_query_fetch_dev: query is NULL"); return -1; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0) {
+        if (Yq_dev) PMK_HIP(hipMemcpyAsync(Yq_dev, q->d_yq, sizeof(double) * (size_t)q->Nq, hipMemcpyDeviceToDevice, c->stream));
+        if (Vq_dev) PMK_HIP(hipMemcpyAsync(Vq_dev, q->d_vq, sizeof(double) * (size_t)q->Nq, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+}
+
 int pmk_query_debug(pmk_query *q, int64_t *home, int64_t *item_offsets, int64_t *item_region, double *item_t,
                     double *item_w, double *item_u, double *item_v)
 {
@@ -1599,6 +1819,29 @@ int pmk_query_fetch_multi(pmk_query *q, double *Yq, int64_t ldyq, double *Vq)
         if (Vq) PMK_HIP(hipMemcpyAsync(Vq, q->d_vq, sizeof(double) * (size_t)q->Nq, hipMemcpyDeviceToHost, c->stream));
     }
     PMK_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int pmk_query_fetch_multi_dev(pmk_query *q, double *Yq_dev, int64_t ldyq, double *Vq_dev)
+{
+    if (!q) { set_error("pmk_query_fetch_multi_dev: query is NULL"); return -1; }
+    if (!q->mixed_multi || q->R_items < 1) { set_error("pmk_query_fetch_multi_dev: pmk_query_mix_multi has not run"); return -2; }
+    if (Vq_dev && !q->var_items) {
+        set_error("pmk_query_fetch_multi_dev: Vq was not computed (pmk_query_items_multi ran with want_var = 0)");
+        return -3;
+    }
+    if (Yq_dev && ldyq < q->Nq) {
+        set_error("pmk_query_fetch_multi_dev: ldyq = %lld < Nq = %lld", (long long)ldyq, (long long)q->Nq);
+        return -4;
+    }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0) {
+        if (Yq_dev)
+            PMK_HIP(hipMemcpy2DAsync(Yq_dev, sizeof(double) * (size_t)ldyq, q->d_yqm, sizeof(double) * (size_t)q->Nq,
+                                     sizeof(double) * (size_t)q->Nq, (size_t)q->R_items, hipMemcpyDeviceToDevice, c->stream));
+        if (Vq_dev) PMK_HIP(hipMemcpyAsync(Vq_dev, q->d_vq, sizeof(double) * (size_t)q->Nq, hipMemcpyDeviceToDevice, c->stream));
+    }
     return 0;
 }
 

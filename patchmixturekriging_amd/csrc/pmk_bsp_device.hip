@@ -143,6 +143,13 @@ struct DevBuf {
         all.push_back(p);
         return static_cast<T *>(p);
     }
+    // hand a buffer over to the caller (who frees it)
+    template <typename T>
+    T *release(T *p)
+    {
+        all.erase(std::remove(all.begin(), all.end(), (void *)p), all.end());
+        return p;
+    }
     ~DevBuf()
     {
         for (void *p : all) (void)hipFree(p);
@@ -300,19 +307,32 @@ __global__ void eps_walk_kernel(int64_t N, const double *__restrict__ X, const d
     if (!FILL) cnt[n] = found;
 }
 
+// What the device assignment leaves on the device for its caller to read back (pmk_bsp_assign_device) or to keep (the
+// index list of pmk_model_create_from_bsp).  Everything is owned by `mem` unless released from it.
+struct AssignWork {
+    DevBuf mem;
+    double *dX = nullptr;               // the points, N x D
+    int64_t *loff = nullptr;            // per-point offsets into d_lists [N + 1]
+    int32_t *d_lists = nullptr;         // leaves of every point, in point order
+    int32_t *d_sorted_pt = nullptr;     // points of every leaf, in leaf order (stable: ascending inside a leaf)
+    int64_t total = 0;                  // (point, leaf) pairs
+};
+
+// The device part of organizetrainingsets: counts (blocks: offsets[P + 1] comes back), then -- if `pairs` -- the lists in
+// point order and -- if `sort` -- the stable sort by leaf.  What follows the counts is only enqueued on the stream.
 template <int D>
-int assign_levels(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets, int64_t *inds,
-                  int64_t *list_offsets, int64_t *lists)
+int assign_core(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, const char *who, bool pairs, bool sort,
+                int64_t *offsets, AssignWork &w)
 {
     hipStream_t s = c->stream;
     const int64_t P = t.P;
-    DevBuf mem;
-    double *dX = mem.get<double>((size_t)(N * D));
+    DevBuf &mem = w.mem;
+    double *dX = w.dX = mem.get<double>((size_t)(N * D));
     double *d_v = mem.get<double>((size_t)((P - 1) * D)), *d_c = mem.get<double>((size_t)(P - 1));
     int32_t *cnt = mem.get<int32_t>((size_t)N + 1);
-    int64_t *loff = mem.get<int64_t>((size_t)N + 1);
+    int64_t *loff = w.loff = mem.get<int64_t>((size_t)N + 1);
     unsigned long long *leaf_cnt = mem.get<unsigned long long>((size_t)P);
-    if (!dX || !d_v || !d_c || !cnt || !loff || !leaf_cnt) { set_error("pmk_bsp_assign_device: out of device memory"); return -100; }
+    if (!dX || !d_v || !d_c || !cnt || !loff || !leaf_cnt) { set_error("%s: out of device memory", who); return -100; }
     PMK_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)(N * D), hipMemcpyDefault, s));
     PMK_HIP(hipMemcpyAsync(d_v, t.v.data(), sizeof(double) * t.v.size(), hipMemcpyHostToDevice, s));
     PMK_HIP(hipMemcpyAsync(d_c, t.c.data(), sizeof(double) * t.c.size(), hipMemcpyHostToDevice, s));
@@ -325,43 +345,72 @@ int assign_levels(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, do
     PMK_HIP(hipStreamSynchronize(s));
     offsets[0] = 0;
     for (int64_t r = 0; r < P; ++r) offsets[r + 1] = offsets[r] + (int64_t)hcnt[(size_t)r];
-    if (!inds && !list_offsets && !lists) return 0;
-    const int64_t total = offsets[P];
-    if (total >= 0x7fffffff) { set_error("pmk_bsp_assign_device: too many (point, leaf) pairs"); return -5; }
+    if (!pairs) return 0;
+    const int64_t total = w.total = offsets[P];
+    if (total >= 0x7fffffff) { set_error("%s: too many (point, leaf) pairs", who); return -5; }
     // per-point offsets, then the lists and the (leaf, point) pairs in point order
     size_t need_scan = 0, need_sort = 0;
-    int32_t *d_lists = mem.get<int32_t>((size_t)total), *d_pt = mem.get<int32_t>((size_t)total);
-    int32_t *d_keys = mem.get<int32_t>((size_t)total), *d_sorted_pt = mem.get<int32_t>((size_t)total);
+    int32_t *d_lists = w.d_lists = mem.get<int32_t>((size_t)total), *d_pt = mem.get<int32_t>((size_t)total);
+    int32_t *d_keys = mem.get<int32_t>((size_t)total), *d_sorted_pt = w.d_sorted_pt = mem.get<int32_t>((size_t)total);
     int bits = 1;
     while (((int64_t)1 << bits) < P) ++bits;
     PMK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need_scan, cnt, loff, (int)(N + 1), s));
     PMK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, d_lists, d_keys, d_pt, d_sorted_pt, (int)total, 0, bits, s));
     const size_t tmp_bytes = std::max(need_scan, need_sort);
     void *d_tmp = mem.get<char>(tmp_bytes);
-    if (!d_lists || !d_pt || !d_keys || !d_sorted_pt || !d_tmp) { set_error("pmk_bsp_assign_device: out of device memory"); return -100; }
+    if (!d_lists || !d_pt || !d_keys || !d_sorted_pt || !d_tmp) { set_error("%s: out of device memory", who); return -100; }
     size_t tb = tmp_bytes;
     PMK_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, cnt, loff, (int)(N + 1), s));
     hipLaunchKernelGGL((eps_walk_kernel<D, true>), dim3(blocks_for(N, 256)), dim3(256), 0, s, N, dX, d_v, d_c, P, eps, cnt,
                        leaf_cnt, loff, d_lists, d_pt, t.dot_mode);
     PMK_HIP(hipGetLastError());
-    std::vector<int32_t> h32((size_t)std::max<int64_t>(total, 1));
-    if (inds && total > 0) {
+    if (sort && total > 0) {
         // stable sort by leaf: within a leaf the points stay in ascending order (X_set_inds, partition.jl:320-330)
         tb = tmp_bytes;
         PMK_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_lists, d_keys, d_pt, d_sorted_pt, (int)total, 0, bits, s));
-        PMK_HIP(hipMemcpyAsync(h32.data(), d_sorted_pt, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+    }
+    return 0;
+}
+
+template <int D>
+int assign_levels(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets, int64_t *inds,
+                  int64_t *list_offsets, int64_t *lists)
+{
+    hipStream_t s = c->stream;
+    AssignWork w;
+    if (int rc = assign_core<D>(c, t, N, X, eps, "pmk_bsp_assign_device", inds || list_offsets || lists, inds != nullptr,
+                                offsets, w))
+        return rc;
+    if (!inds && !list_offsets && !lists) return 0;
+    const int64_t total = w.total;
+    std::vector<int32_t> h32((size_t)std::max<int64_t>(total, 1));
+    if (inds && total > 0) {
+        PMK_HIP(hipMemcpyAsync(h32.data(), w.d_sorted_pt, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
         PMK_HIP(hipStreamSynchronize(s));
         for (int64_t i = 0; i < total; ++i) inds[i] = h32[(size_t)i];
     }
     if (lists && total > 0) {
-        PMK_HIP(hipMemcpyAsync(h32.data(), d_lists, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+        PMK_HIP(hipMemcpyAsync(h32.data(), w.d_lists, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
         PMK_HIP(hipStreamSynchronize(s));
         for (int64_t i = 0; i < total; ++i) lists[i] = h32[(size_t)i];
     }
     if (list_offsets) {
-        PMK_HIP(hipMemcpyAsync(list_offsets, loff, sizeof(int64_t) * (size_t)(N + 1), hipMemcpyDeviceToHost, s));
+        PMK_HIP(hipMemcpyAsync(list_offsets, w.loff, sizeof(int64_t) * (size_t)(N + 1), hipMemcpyDeviceToHost, s));
         PMK_HIP(hipStreamSynchronize(s));
     }
+    return 0;
+}
+
+// the eps-sets of every leaf as a device index list (pmk_model_create_from_bsp): the assignment above, stopped before the
+// download.  The caller takes over *d_inds [offsets[P]] and *d_X [N x D] and frees them with hipFree.
+template <int D>
+int assign_keep(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets, int32_t **d_inds,
+                double **d_X)
+{
+    AssignWork w;
+    if (int rc = assign_core<D>(c, t, N, X, eps, "pmk_model_create_from_bsp", true, true, offsets, w)) return rc;
+    *d_inds = w.mem.release(w.d_sorted_pt);
+    *d_X = w.mem.release(w.dX);
     return 0;
 }
 
@@ -382,6 +431,38 @@ int bsp_assign_device(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X
     case 3: return assign_levels<3>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
     case 4: return assign_levels<4>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
     default: set_error("pmk_bsp_assign_device: D=%d outside 1..%d", t.D, MAX_D); return -1;
+    }
+}
+
+// The patches of a model as one device index list.  eps >= 0: the eps-set of every leaf, exactly the lists of
+// bsp_assign_device; eps < 0: the tree's own leaf lists (X_parts_inds of setuppartition; the caller has checked N == t.N).
+// offsets[P + 1] on the host; *d_inds [offsets[P]] and *d_X (the points, N x D) on the device, owned by the caller.  Blocks.
+int bsp_patch_index_device(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X, double eps, int64_t *offsets,
+                           int32_t **d_inds, double **d_X)
+{
+    *d_inds = nullptr;
+    *d_X = nullptr;
+    if (eps < 0) {
+        hipStream_t s = c->stream;
+        DevBuf mem;
+        double *dX = mem.get<double>((size_t)(N * t.D));
+        int32_t *di = mem.get<int32_t>((size_t)N);
+        if (!dX || !di) { set_error("pmk_model_create_from_bsp: out of device memory"); return -100; }
+        std::vector<int32_t> h32(t.leaf_inds.begin(), t.leaf_inds.end());
+        PMK_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)(N * t.D), hipMemcpyDefault, s));
+        PMK_HIP(hipMemcpyAsync(di, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice, s));
+        PMK_HIP(hipStreamSynchronize(s));
+        for (int64_t r = 0; r <= t.P; ++r) offsets[r] = t.leaf_off[(size_t)r];
+        *d_inds = mem.release(di);
+        *d_X = mem.release(dX);
+        return 0;
+    }
+    switch (t.D) {
+    case 1: return assign_keep<1>(c, t, N, X, eps, offsets, d_inds, d_X);
+    case 2: return assign_keep<2>(c, t, N, X, eps, offsets, d_inds, d_X);
+    case 3: return assign_keep<3>(c, t, N, X, eps, offsets, d_inds, d_X);
+    case 4: return assign_keep<4>(c, t, N, X, eps, offsets, d_inds, d_X);
+    default: set_error("pmk_model_create_from_bsp: D=%d outside 1..%d", t.D, MAX_D); return -1;
     }
 }
 

@@ -153,6 +153,17 @@ struct pmk_model {
     uint32_t *d_loo_cnt = nullptr;      // 8 queue heads
     int64_t loo_ntasks = 0;
     int32_t loo_qoff[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // built by pmk_model_create_from_bsp (pmk_gather.hip): row i of patch r is the global point d_pidx[pidx_off[r] + i].
+    // The *_global setters gather through this list; the chunk prefix (one entry per 256 slab rows of a patch) is the
+    // grid of the gather kernels.
+    bool from_bsp = false;
+    int64_t N_global = 0;
+    std::vector<int64_t> pidx_off;      // P + 1 (host copy)
+    int64_t *d_pidx_off = nullptr;      // P + 1
+    int32_t *d_pidx = nullptr;          // pidx_off[P]
+    int32_t *d_gchunk = nullptr;        // P + 1: prefix over ceil(ld_r / 256)
+    int64_t gchunks = 0;
+    double *d_gstage = nullptr; size_t gstage_bytes = 0;   // device copy of a host array handed to a *_global setter (grow only)
 };
 
 struct pmk_query {
@@ -217,6 +228,9 @@ namespace pmk {
     int launch_items_multi_patches(pmk_query *q, hipStream_t s);                                                     \
     int launch_evidence(const pmk_model *m, int R, double *d_logdet, double *d_quad, hipStream_t s);                 \
     int launch_loo_values(const pmk_model *m, int R, double *d_res, double *d_var, hipStream_t s);                   \
+    int launch_gather_points(const pmk_model *m, const double *d_X, const double *d_y, hipStream_t s);               \
+    int launch_gather_vector(const pmk_model *m, const double *d_src, void *d_dst, hipStream_t s);                   \
+    int launch_gather_multi(const pmk_model *m, int R, const double *d_Y, int64_t ldy, hipStream_t s);               \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)

@@ -30,6 +30,9 @@ static int no_gpu(const char *what)
     int launch_items_multi_patches(pmk_query *, hipStream_t) { return no_gpu("launch_items_multi_patches"); }       \
     int launch_evidence(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_evidence"); } \
     int launch_loo_values(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_loo_values"); } \
+    int launch_gather_points(const pmk_model *, const double *, const double *, hipStream_t) { return no_gpu("launch_gather_points"); } \
+    int launch_gather_vector(const pmk_model *, const double *, void *, hipStream_t) { return no_gpu("launch_gather_vector"); } \
+    int launch_gather_multi(const pmk_model *, int, const double *, int64_t, hipStream_t) { return no_gpu("launch_gather_multi"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -54,6 +57,10 @@ int bsp_build_device(pmk_ctx *, int, int64_t, const double *, int, int, int, Bsp
 int bsp_assign_device(pmk_ctx *, const BspArrays &, int64_t, const double *, double, int64_t *, int64_t *, int64_t *, int64_t *)
 {
     return no_gpu("bsp_assign_device");
+}
+int bsp_patch_index_device(pmk_ctx *, const BspArrays &, int64_t, const double *, double, int64_t *, int32_t **, double **)
+{
+    return no_gpu("bsp_patch_index_device");
 }
 
 }  // namespace pmk

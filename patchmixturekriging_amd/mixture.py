@@ -26,6 +26,81 @@ def _i(a):
     return a.ctypes.data_as(_ip)
 
 
+class GlobalArray:
+    """a float64 array of all points, on the host (numpy) or on the device (anything with __cuda_array_interface__, such
+    as a torch tensor): address, shape and strides in elements, validated without any device call.  `keep` holds the
+    owner alive while the library reads it."""
+
+    def __init__(self, a, what):
+        self.keep = a
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float64:
+                raise ValueError("%s must be float64, not %s" % (what, a.dtype))
+            self.device, self.ptr, self.shape = False, a.ctypes.data, tuple(a.shape)
+            strides = a.strides
+        else:
+            try:
+                cai = a.__cuda_array_interface__
+            except (AttributeError, TypeError, RuntimeError):
+                raise ValueError("%s must be a numpy array or a device array (__cuda_array_interface__), not %s"
+                                 % (what, type(a).__name__))
+            if cai["typestr"] not in ("<f8", "=f8", "|f8"):
+                raise ValueError("%s must be float64, not %s" % (what, cai["typestr"]))
+            self.device, self.ptr, self.shape = True, int(cai["data"][0]), tuple(int(v) for v in cai["shape"])
+            strides = cai.get("strides")
+            if strides is None:                 # C-contiguous
+                strides, acc = [], 8
+                for v in reversed(self.shape):
+                    strides.insert(0, acc)
+                    acc *= max(v, 1)
+        if any(int(v) % 8 for v in strides):
+            raise ValueError("%s: strides must be whole float64 elements" % what)
+        self.strides = tuple(int(v) // 8 for v in strides)
+        self.what = what
+
+    def vector(self, N):
+        """N contiguous values"""
+        if self.shape != (int(N),):
+            raise ValueError("%s must have shape (%d,), not %s" % (self.what, N, self.shape))
+        if N > 1 and self.strides != (1,):
+            raise ValueError("%s must be contiguous" % self.what)
+        return self
+
+    def points(self, D=None):
+        """point-major (N, D), C-contiguous"""
+        if len(self.shape) != 2 or (D is not None and self.shape[1] != D):
+            raise ValueError("%s must have shape (N, %s), not %s" % (self.what, "D" if D is None else D, self.shape))
+        N, D = self.shape
+        if N * D > 0 and (self.strides[1] != 1 and D > 1 or self.strides[0] != D and N > 1):
+            raise ValueError("%s must be C-contiguous" % self.what)
+        return self
+
+    def columns(self, N):
+        """(N, R) column-major with leading dimension ld >= N (a vector is one column) -> R, ld"""
+        if len(self.shape) == 1:
+            self.vector(N)
+            return 1, max(int(N), 1)
+        if len(self.shape) != 2 or self.shape[0] != int(N):
+            raise ValueError("%s must have shape (%d, R), not %s" % (self.what, N, self.shape))
+        R = self.shape[1]
+        if not 1 <= R <= MAX_OUTPUTS:
+            raise ValueError("R = %d target columns, outside 1..%d" % (R, MAX_OUTPUTS))
+        if N > 1 and self.strides[0] != 1:
+            raise ValueError("%s must be column-major (Fortran order)" % self.what)
+        ld = self.strides[1] if R > 1 else max(int(N), 1)
+        if ld < N:
+            raise ValueError("%s: leading dimension %d < N = %d" % (self.what, ld, N))
+        return R, ld
+
+
+def _refuse_closure_kernel(theta, who):
+    """the tree route packs the tree's own D coordinates: the closure-carrying (warp-feature and DPP) kernels evaluate on
+    more coordinates than the tree has, or need a point-dependent diagonal term"""
+    if hasattr(theta, "diag_addend") or getattr(theta, "warped", False):
+        raise TypeError("%s: closure-carrying kernels (%s) are not available on a model built from a tree and global "
+                        "points; build the model from lists of patches" % (who, type(theta).__name__))
+
+
 class PosDefException(np.linalg.LinAlgError):
     """cholesky(U) of the reference throws PosDefException(k) (mixtureGP.jl:109)"""
 
@@ -42,6 +117,7 @@ class DeviceModel:
     def __init__(self, X_parts, y_parts, ctx=None, _factors=None, dtype="f64"):
         self.ctx = ctx or default_context()
         L = self.ctx.L
+        self._from_tree = False
         self.X = [as_points(x) for x in X_parts]
         self.P = len(self.X)
         if self.P == 0:
@@ -76,6 +152,97 @@ class DeviceModel:
         self._loo_done = False
         self._multi_solved = False
         self._has_kernels = False       # a fit records its kernels; a model built from factors needs set_kernels
+
+    @classmethod
+    def from_tree(cls, root, X, y=None, eps=None, ctx=None, dtype="f64", leaf_base=0, P=None):
+        """pmk_model_create_from_bsp: the model of the tree `root` and ONE global point array X (N, D), numpy or a device
+        array (a torch tensor), float64 and contiguous; y likewise, N targets, or None (zero until set_targets_global).
+        eps=None: patch r is the tree's own leaf leaf_base + r; eps >= 0: its eps-set (organizetrainingsets).  The
+        library assigns, gathers and packs on the GPU; the tree is attached.  The result equals
+        DeviceModel(X_set, y_set) on the host-cut lists bit for bit."""
+        xa = GlobalArray(X, "X").points(getattr(root, "_D", None))
+        N = xa.shape[0]
+        ya = None if y is None else GlobalArray(y, "y").vector(N)
+        if dtype not in ("f64", "f32"):
+            raise ValueError("dtype must be 'f64' or 'f32'")
+        if eps is not None and not float(eps) >= 0:
+            raise ValueError("eps must be None (the tree's leaves) or >= 0")
+        if N < 1:
+            raise ValueError("no points")
+        nat = _native(root)
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context()
+        L = self.ctx.L
+        h = C.c_void_p()
+        _lib.check(L.pmk_model_create_from_bsp(self.ctx.h, nat.h, N, xa.ptr, None if ya is None else ya.ptr,
+                                               -1.0 if eps is None else float(eps), int(leaf_base), int(P or 0),
+                                               {"f64": 0, "f32": 1}[dtype], C.byref(h)), "pmk_model_create_from_bsp")
+        self.h = h
+        self.dtype, self.D, self.N = dtype, xa.shape[1], N
+        self._from_tree, self._X, self._X_global = True, None, (None if xa.device else X)
+        self.leaf_base = int(leaf_base)
+        self.P = int(L.pmk_model_num_patches(h))
+        self._index = None
+        off, _ = self.patch_index()
+        self.n = np.diff(off)
+        self.theta = self.sigma2 = None
+        self._has_factor, self._has_targets = False, True
+        self._loo_done = self._multi_solved = self._has_kernels = False
+        return self
+
+    @property
+    def X(self):
+        """the points of every patch; on a model built by from_tree they are cut from the index list on first use, and
+        only if X was a host array (None otherwise: the points never came to the host)"""
+        if self._X is None and getattr(self, "_X_global", None) is not None:
+            off, inds = self.patch_index()
+            self._X = [self._X_global[inds[off[r]:off[r + 1]]] for r in range(self.P)]
+        return self._X
+
+    @X.setter
+    def X(self, value):
+        self._X = value
+
+    def _need_tree_model(self, who):
+        if not getattr(self, "_from_tree", False):
+            raise _lib.PmkError("%s: the model was built from lists of patches, not by from_tree" % who)
+
+    def patch_index(self):
+        """pmk_model_patch_index -> (offsets [P+1], inds): row i of patch r is the global point inds[offsets[r] + i]"""
+        self._need_tree_model("patch_index")
+        if self._index is None:
+            L = self.ctx.L
+            off = np.empty(self.P + 1, dtype=np.int64)
+            _lib.check(L.pmk_model_patch_index(self.h, None, _i(off), None), "pmk_model_patch_index")
+            inds = np.empty(max(int(off[-1]), 1), dtype=np.int64)
+            _lib.check(L.pmk_model_patch_index(self.h, None, None, _i(inds)), "pmk_model_patch_index")
+            self._index = (off, inds[:int(off[-1])])
+        return self._index
+
+    def set_targets_global(self, y):
+        """pmk_model_set_targets_global: the N targets of ALL points (numpy or device array) through the index list.
+        With a device array this only enqueues on the context's stream."""
+        self._need_tree_model("set_targets_global")
+        ya = GlobalArray(y, "y").vector(self.N)
+        _lib.check(self.ctx.L.pmk_model_set_targets_global(self.h, ya.ptr), "pmk_model_set_targets_global")
+        self._has_factor = False
+
+    def set_targets_multi_global(self, Y):
+        """pmk_model_set_targets_multi_global: Y is (N, R) column-major (Fortran order; its column stride is the leading
+        dimension), or a vector for R = 1"""
+        self._need_tree_model("set_targets_multi_global")
+        ya = GlobalArray(Y, "Y")
+        R, ld = ya.columns(self.N)
+        _lib.check(self.ctx.L.pmk_model_set_targets_multi_global(self.h, R, ya.ptr, ld), "pmk_model_set_targets_multi_global")
+        self.R = R
+        self._multi_solved = False
+
+    def set_diag_global(self, diag):
+        """pmk_model_set_diag_global: N addends of the kernel's diagonal through the index list (None clears it)"""
+        self._need_tree_model("set_diag_global")
+        da = None if diag is None else GlobalArray(diag, "diag").vector(self.N)
+        self._has_factor = False
+        _lib.check(self.ctx.L.pmk_model_set_diag_global(self.h, None if da is None else da.ptr), "pmk_model_set_diag_global")
 
     @classmethod
     def from_factors(cls, X_parts, c_set, L_set, ctx=None):
@@ -117,6 +284,8 @@ class DeviceModel:
 
     def fit(self, theta, sigma2):
         """enqueue kernel build + Cholesky + solves for every patch"""
+        if getattr(self, "_from_tree", False):
+            _refuse_closure_kernel(theta, "fit")
         d = theta.desc()
         _lib.check(self.ctx.L.pmk_model_fit(self.h, C.byref(d), float(sigma2)), "pmk_model_fit")
         self.theta, self.sigma2 = theta, float(sigma2)
@@ -272,10 +441,18 @@ class DeviceQuery:
 
     def __init__(self, model, Xq):
         self.model = model
-        self.Xq = as_points(Xq)
-        self.Nq = self.Xq.shape[0]
+        if isinstance(Xq, np.ndarray) or not hasattr(Xq, "__cuda_array_interface__"):
+            self.Xq = as_points(Xq)
+            ptr = _d(self.Xq)
+        else:                                   # a device array (torch tensor): no host copy
+            xa = GlobalArray(Xq, "Xq").points(model.D)
+            self.Xq, self._keep = None, Xq
+            ptr = C.cast(C.c_void_p(xa.ptr), _dp)
+            self.Nq = xa.shape[0]
+        if self.Xq is not None:
+            self.Nq = self.Xq.shape[0]
         h = C.c_void_p()
-        _lib.check(model.ctx.L.pmk_query_create(model.h, self.Nq, _d(self.Xq), C.byref(h)), "pmk_query_create")
+        _lib.check(model.ctx.L.pmk_query_create(model.h, self.Nq, ptr, C.byref(h)), "pmk_query_create")
         self.h = h
         self.L = model.ctx.L
         self.has_diag = False
@@ -393,6 +570,34 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_fetch(self.h, _d(Yq), _d(Vq)), "pmk_query_fetch")
         return Yq, Vq
 
+    @staticmethod
+    def _device_out(a, what):
+        ga = GlobalArray(a, what)
+        if not ga.device:
+            raise ValueError("%s must be a device array (__cuda_array_interface__); fetch() returns host arrays" % what)
+        return ga
+
+    def fetch_into(self, Yq, Vq=None):
+        """pmk_query_fetch_dev: the mixed results into device arrays of Nq float64 (torch tensors): device-to-device on
+        the context's stream, no host synchronisation"""
+        ya = self._device_out(Yq, "Yq").vector(self.Nq)
+        va = None if Vq is None else self._device_out(Vq, "Vq").vector(self.Nq)
+        _lib.check(self.L.pmk_query_fetch_dev(self.h, ya.ptr, None if va is None else va.ptr), "pmk_query_fetch_dev")
+
+    def fetch_multi_into(self, Yq, Vq=None):
+        """pmk_query_fetch_multi_dev: Yq is a device array (Nq, R) in column-major order (its column stride is the leading
+        dimension); Vq (Nq) only if the items ran with the variance"""
+        R = getattr(self.model, "R", 0)
+        ya = self._device_out(Yq, "Yq")
+        if len(ya.shape) != 2 or ya.shape[1] != R:
+            raise ValueError("Yq must have shape (%d, %d), not %s" % (self.Nq, R, ya.shape))
+        _, ld = ya.columns(self.Nq)
+        if Vq is not None and not getattr(self, "variance", False):
+            raise ValueError("Vq was not computed: the items ran mean-only (variance=False)")
+        va = None if Vq is None else self._device_out(Vq, "Vq").vector(self.Nq)
+        _lib.check(self.L.pmk_query_fetch_multi_dev(self.h, ya.ptr, ld, None if va is None else va.ptr),
+                   "pmk_query_fetch_multi_dev")
+
     def items_multi(self, theta, variance=True):
         d = theta.desc()
         _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
@@ -495,7 +700,7 @@ class _LazyFactors:
         self._eta, self._what, self._cache = eta, what, {}
 
     def __len__(self):
-        return len(self._eta.X_parts)
+        return len(self._eta.c_set)
 
     def __getitem__(self, r):
         if r not in self._cache:
@@ -509,8 +714,11 @@ class MixtureGPType:
     """MixtureGPType(X_parts, hps)   (mixtureGP.jl:38-66)"""
 
     def __init__(self, X_parts, hps):
+        self._from_tree = False
         self.X_parts = [as_points(x) for x in X_parts]
-        N = len(self.X_parts)
+        self._setup(len(self.X_parts), hps)
+
+    def _setup(self, N, hps):
         self.c_set = [None] * N
         self.sigma2_set = [None] * N
         self.hps = hps
@@ -518,19 +726,64 @@ class MixtureGPType:
         self.U_set = _LazyFactors(self, GET_K)      # K without noise (mixtureGP.jl:99)
         self.L_set = _LazyFactors(self, GET_L)      # cholesky(U).L    (mixtureGP.jl:112)
 
+    @classmethod
+    def from_tree(cls, root, X, eps=None, hps=None, ctx=None, dtype="f64"):
+        """MixtureGPType on the patches of a tree, built on the device from ONE global point array (numpy or a device
+        array): DeviceModel.from_tree.  eps=None: the tree's leaves (setuppartition); eps >= 0: the eps-sets
+        (organizetrainingsets).  On such an eta fitmixtureGP_ / _multi_ / _patches_ take the GLOBAL targets (N values, or
+        N x R) and refit this resident model: no model is created per call."""
+        model = DeviceModel.from_tree(root, X, None, eps, ctx, dtype)
+        self = cls.__new__(cls)
+        self._from_tree = True
+        self._X_parts = None
+        self._setup(model.P, hps)
+        self._model = self._tree_model = model
+        return self
 
-def fitmixtureGP_(eta, y_parts, theta, sigma2):
-    """fitmixtureGP!(η, y_parts, θ, σ²) -> η   (mixtureGP.jl:70-118)"""
-    model, cs, info = fit_patches(eta.X_parts, y_parts, theta, sigma2)
-    bad = np.nonzero(info)[0]
-    if len(bad):
-        raise PosDefException(int(bad[0]), int(info[bad[0]]))
+    @property
+    def X_parts(self):
+        """the points of every patch (on an eta built by from_tree: cut on first use, None for a device X)"""
+        if self._X_parts is None and self._from_tree:
+            return self._tree_model.X
+        return self._X_parts
+
+    @X_parts.setter
+    def X_parts(self, value):
+        self._X_parts = value
+
+    def __len__(self):
+        return len(self.c_set)
+
+
+def _store_fit(eta, model, cs, sigma2s):
     eta._model = model
     eta.U_set._cache.clear()
     eta.L_set._cache.clear()
     for r in range(len(cs)):
         eta.c_set[r] = cs[r]
-        eta.sigma2_set[r] = float(sigma2)
+        eta.sigma2_set[r] = float(sigma2s[r])
+
+
+def _raise_if_failed(info):
+    bad = np.nonzero(info)[0]
+    if len(bad):
+        raise PosDefException(int(bad[0]), int(info[bad[0]]))
+
+
+def fitmixtureGP_(eta, y_parts, theta, sigma2):
+    """fitmixtureGP!(η, y_parts, θ, σ²) -> η   (mixtureGP.jl:70-118).  On an eta built by MixtureGPType.from_tree
+    y_parts is the GLOBAL target vector (numpy or device array) and the resident model is refitted."""
+    if getattr(eta, "_from_tree", False):
+        _refuse_closure_kernel(theta, "fitmixtureGP_")
+        model = eta._tree_model
+        model.set_targets_global(y_parts)
+        model.fit(theta, sigma2)
+        _raise_if_failed(model.info())
+        _store_fit(eta, model, model.weights(), [sigma2] * model.P)
+        return eta
+    model, cs, info = fit_patches(eta.X_parts, y_parts, theta, sigma2)
+    _raise_if_failed(info)
+    _store_fit(eta, model, cs, [sigma2] * len(cs))
     return eta
 
 
@@ -620,6 +873,18 @@ def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
     """fitmixtureGP! (mixtureGP.jl:70-118) with R target columns per patch that share one factor: the fit runs once on
     column 0 (c_set, L_set as fitmixtureGP_ leaves them), then every column is solved from the resident factor
     (c = U \\ y of mixtureGP.jl:106 for R right-hand sides).  Stores eta.C_set (a list of n_r x R)."""
+    if getattr(eta, "_from_tree", False):
+        # Y_parts is the GLOBAL (N, R) column-major array; its first column is N contiguous values
+        _refuse_closure_kernel(theta, "fitmixtureGP_multi_")
+        model = eta._tree_model
+        ya = GlobalArray(Y_parts, "Y")
+        ya.columns(model.N)
+        col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
+        fitmixtureGP_(eta, col0, theta, sigma2)
+        model.set_targets_multi_global(Y_parts)
+        model.solve_multi()
+        eta.C_set = model.weights_multi()
+        return eta
     Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
     fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
     model = eta._model
@@ -695,21 +960,16 @@ def loomixtureGP_multi(eta):
 def fitmixtureGP_patches_(eta, y_parts, thetas, sigma2s):
     """fitmixtureGP! (mixtureGP.jl:70-118) with thetas[r], sigma2s[r] for patch r -> eta.  Fills eta.sigma2_set[r] with
     the patch's own value and eta.theta_set; raises PosDefException(patch, k) like fitmixtureGP_."""
-    patch_hyper(thetas, sigma2s, len(eta.X_parts))
-    model = DeviceModel(eta.X_parts, y_parts)
+    patch_hyper(thetas, sigma2s, len(eta.c_set))
+    if getattr(eta, "_from_tree", False):
+        model = eta._tree_model
+        model.set_targets_global(y_parts)           # the GLOBAL targets; the resident model is refitted
+    else:
+        model = DeviceModel(eta.X_parts, y_parts)
     model.fit_patches(thetas, sigma2s)
-    info = model.info()
-    bad = np.nonzero(info)[0]
-    if len(bad):
-        raise PosDefException(int(bad[0]), int(info[bad[0]]))
-    cs = model.weights()
-    eta._model = model
-    eta.U_set._cache.clear()
-    eta.L_set._cache.clear()
+    _raise_if_failed(model.info())
+    _store_fit(eta, model, model.weights(), sigma2s)
     eta.theta_set = list(thetas)
-    for r in range(len(cs)):
-        eta.c_set[r] = cs[r]
-        eta.sigma2_set[r] = float(sigma2s[r])
     return eta
 
 
