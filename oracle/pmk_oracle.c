@@ -283,7 +283,9 @@ static int gethyperplane(int D, const double *X, const int64_t *idx, int64_t n, 
     if (!ev) return -2;
     for (int64_t i = 0; i < n; ++i) ev[i] = dot_seq(D, v, X + idx[i] * D, dot_mode);   /* :69 */
     memcpy(ev + n, ev, sizeof(double) * (size_t)n);
-    *c = pmko_median(n, ev + n);                                     /* :70 */
+    /* :70.  + 0.0: a zero median is stored as +0.0.  Which of the equal keys -0.0 and +0.0 a selection returns is
+     * the algorithm's choice (Julia's partial quicksort, qsort here), and no comparison or |t| downstream sees it. */
+    *c = pmko_median(n, ev + n) + 0.0;
     for (int64_t i = 0; i < n; ++i) left[i] = ev[i] < *c;             /* :72-80 strict */
     free(ev);
     return 0;

@@ -656,7 +656,10 @@ int pmk_model_create_from_bsp(pmk_ctx *ctx, const pmk_bsp *bsp, int64_t N, const
     if (t.D < 1 || t.D > MAX_D) { set_error("pmk_model_create_from_bsp: D=%d outside 1..%d", t.D, MAX_D); return -2; }
     if (N < 1) { set_error("pmk_model_create_from_bsp: no points"); return -3; }
     if (N >= 0x7fffffff) { set_error("pmk_model_create_from_bsp: N must be below 2^31-1"); return -5; }
-    if (!(eps >= 0) && N != t.N) {
+    // only eps < 0 selects the tree's own leaves; a NaN is an eps like any other: it assigns no point to any leaf (every
+    // comparison of find-eps-partitions fails), exactly as pmk_bsp_assign does, and the empty patch is refused below
+    const bool leaves = eps < 0;
+    if (leaves && N != t.N) {
         set_error("pmk_model_create_from_bsp: the tree's own leaves hold %lld points, N = %lld", (long long)t.N, (long long)N);
         return -3;
     }
@@ -670,7 +673,7 @@ int pmk_model_create_from_bsp(pmk_ctx *ctx, const pmk_bsp *bsp, int64_t N, const
     std::vector<int64_t> off((size_t)t.P + 1);
     DevTmp<int32_t> d_all;                       // the index list of ALL leaves
     DevTmp<double> d_X;
-    int rc = bsp_patch_index_device(ctx, t, N, X, eps >= 0 ? eps : -1.0, off.data(), &d_all.p, &d_X.p);
+    int rc = bsp_patch_index_device(ctx, t, N, X, leaves ? -1.0 : eps, off.data(), &d_all.p, &d_X.p);
     if (rc) return rc;
     std::vector<int64_t> n((size_t)P);
     for (int64_t r = 0; r < P; ++r) n[(size_t)r] = off[(size_t)(leaf_base + r + 1)] - off[(size_t)(leaf_base + r)];

@@ -161,7 +161,9 @@ int bsp_build(int D, int64_t N, const double *X, int levels, int sign_mode, int 
             ev.resize((size_t)n);
             for (int64_t i = 0; i < n; ++i) ev[(size_t)i] = dot_seq(D, v, X + idx[i] * D, dot_mode);   // splitpoints :69
             evs = ev;
-            const double c = median_inplace(evs);                        // :70
+            // :70.  + 0.0 makes a zero median +0.0: which of several equal keys (-0.0 == +0.0) is the middle order
+            // statistic depends on the selection algorithm, and nothing downstream sees the sign
+            const double c = median_inplace(evs) + 0.0;
             t.c[(size_t)(heap0 + nd)] = c;
             int64_t nl = 0;                                              // stable partition, left = e < c (:72-80)
             for (int64_t i = 0; i < n; ++i) nl += ev[(size_t)i] < c;

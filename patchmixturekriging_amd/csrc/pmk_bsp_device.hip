@@ -84,7 +84,8 @@ __global__ void median_kernel(int64_t nodes, const int64_t *__restrict__ seg_off
     if (n <= 0) { c[nd] = 0.0; return; }
     const int64_t mid = n / 2;
     const double hi = es[b + mid];
-    c[nd] = (n & 1) ? hi : es[b + mid - 1] / 2.0 + hi / 2.0;
+    // + 0.0: a zero median is +0.0 whatever order the sort left -0.0 and +0.0 in (as in bsp_build of pmk_bsp.cpp)
+    c[nd] = ((n & 1) ? hi : es[b + mid - 1] / 2.0 + hi / 2.0) + 0.0;
 }
 
 __global__ void flag_kernel(int64_t N, const double *__restrict__ e, const int32_t *__restrict__ node_of,

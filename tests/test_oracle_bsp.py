@@ -125,3 +125,111 @@ def test_assign_band_property(seed, D, levels):
         assert np.all(np.diff(sinds[soff[r]:soff[r + 1]]) > 0)
     off, _ = b.leaves()
     assert np.all(np.diff(soff) >= np.diff(off))
+
+
+# ------------------------------------------------------------------------------------ gridded, collinear, duplicated points
+# The host build and eps-assignment (pmk_bsp.cpp, which the GPU tests hold the device to) against the oracle on inputs
+# where projections EQUAL hyperplane offsets, tie with one another, or leave leaves empty: tests/_degenerate.py.
+import patchmixturekriging_amd as pmk
+from patchmixturekriging_amd import partition as PT
+
+import _degenerate as G
+
+_TREES = {}
+
+
+def _trees(name, sign_mode, dot_mode):
+    """host tree and oracle tree of one input in one mode pair, built once"""
+    key = (name, sign_mode, dot_mode)
+    if key not in _TREES:
+        X, levels = G.BUILDS[name]
+        root, _, inds = pmk.setuppartition(X, levels, sign_mode=sign_mode, dot_mode=dot_mode)
+        _TREES[key] = (root, inds, O.BSP(X, levels, sign_mode=sign_mode, dot_mode=dot_mode))
+    return _TREES[key]
+
+
+@pytest.mark.parametrize("sign_mode,dot_mode", G.MODES)
+@pytest.mark.parametrize("name", list(G.BUILDS))
+def test_degenerate_build_host_vs_oracle(name, sign_mode, dot_mode):
+    X, levels = G.BUILDS[name]
+    root, inds, ob = _trees(name, sign_mode, dot_mode)
+    hv, hc = PT.hyperplane_arrays(root)
+    ov, oc = ob.hyperplanes()
+    assert np.array_equal(G.bits(hv), G.bits(ov))
+    assert np.array_equal(hc, oc) and np.array_equal(np.signbit(hc), np.signbit(oc))
+    assert np.array_equal(G.bits(hc), G.bits(oc))          # a zero offset is +0.0 on both sides
+    assert not np.any(np.signbit(hc) & (hc == 0))
+    off, oi = ob.leaves()
+    assert np.array_equal(np.cumsum([0] + [len(i) for i in inds]), off) and np.array_equal(np.concatenate(inds), oi)
+    E = G.projections(ov, oc, X, dot_mode)
+    on_plane, zero_c, empty = int((E == oc[:, None]).sum()), int((oc == 0).sum()), int((np.diff(off) == 0).sum())
+    print("%s (%d, %d): %d (point, plane) pairs with e == c, %d offsets equal to zero, %d empty leaves, leaf sizes %s"
+          % (name, sign_mode, dot_mode, on_plane, zero_c, empty, np.diff(off).tolist() if levels < 6 else "..."))
+    assert on_plane > 0                                      # every input puts points exactly on a hyperplane
+    if name in ("lattice33x31", "pm0_1d", "collinear"):
+        assert zero_c > 0
+    if name == "dups5":
+        assert np.array_equal(np.diff(off), [0, 100, 0, 100, 0, 100, 100, 100])
+    else:
+        assert empty == 0
+
+
+@pytest.mark.parametrize("sign_mode,dot_mode", G.MODES)
+@pytest.mark.parametrize("name", list(G.BUILDS))
+def test_degenerate_eps_assignment_host_vs_oracle(name, sign_mode, dot_mode):
+    X, levels = G.BUILDS[name]
+    root, _, ob = _trees(name, sign_mode, dot_mode)
+    ov, oc = ob.hyperplanes()
+    E = G.projections(ov, oc, X, dot_mode)
+    N, P = len(X), ob.P
+    for eps in G.eps_list(name):
+        X_set, X_set_inds, regions, _ = pmk.organizetrainingsets(root, levels, X, eps)
+        soff, sinds, loff, lists = ob.assign(X, eps)
+        assert np.array_equal(np.cumsum([0] + [len(i) for i in X_set_inds]), soff)
+        assert np.array_equal(np.concatenate(X_set_inds), sinds)
+        assert np.array_equal(np.cumsum([0] + [len(l) for l in regions]), loff)
+        assert np.array_equal(np.concatenate(regions), lists)
+        for xs, ix in zip(X_set, X_set_inds):
+            assert np.array_equal(G.bits(xs), G.bits(X[ix]))
+        per_point = np.diff(loff)
+        nowhere, everywhere, total = int((per_point == 0).sum()), int((per_point == P).sum()), int(soff[-1])
+        with np.errstate(invalid="ignore"):
+            on_band = int(((E == (oc + eps)[:, None]) | (E == (oc - eps)[:, None])).sum())
+        print("%s (%d, %d) eps=%r: %d pairs, %d points in no leaf, %d in every leaf, %d empty sets, %d (point, plane) "
+              "pairs with e == c +- eps" % (name, sign_mode, dot_mode, eps, total, nowhere, everywhere,
+                                            int((np.diff(soff) == 0).sum()), on_band))
+        if eps == 0.0:
+            assert 0 < nowhere and total == N - nowhere     # a point with e == c on its way down is in no leaf
+        if np.isnan(eps):
+            assert total == 0 and nowhere == N
+        if eps in (float("inf"), 1e300):
+            assert total == N * P and everywhere == N
+        if eps == -0.1:
+            assert total < N
+        if name == "pm0_1d" and eps in (0.5, 1.0):
+            assert on_band > 0
+            # strict at the root: e == c + eps is not left of it, e == c - eps not right of it
+            for n in np.nonzero(E[0] == oc[0] + eps)[0]:
+                assert np.all(regions[n] >= P // 2)
+            for n in np.nonzero(E[0] == oc[0] - eps)[0]:
+                assert np.all(regions[n] < P // 2)
+            if eps == 1.0:
+                assert np.any(E[0] == oc[0] + eps) and np.any(E[0] == oc[0] - eps)
+
+
+@pytest.mark.parametrize("name", list(G.REFUSED))
+def test_degenerate_refusals_host_vs_oracle(name):
+    X, levels, status, text, node, depth = G.REFUSED[name]
+    for sign_mode, dot_mode in G.MODES:
+        with pytest.raises(pmk.PmkError) as err:
+            pmk.setuppartition(X, levels, sign_mode=sign_mode, dot_mode=dot_mode)
+        assert "(%d): " % status in str(err.value) and text in str(err.value), str(err.value)
+        with pytest.raises(RuntimeError):                   # gethyperplane of an empty node
+            O.BSP(X, levels, sign_mode=sign_mode, dot_mode=dot_mode)
+        # the oracle one level short of its refusal: the node is its first empty leaf, and no shallower tree has one
+        sizes = np.diff(O.BSP(X, depth + 1, sign_mode=sign_mode, dot_mode=dot_mode).leaves()[0])
+        assert int(np.argmax(sizes == 0)) == node and sizes[node] == 0 and depth + 1 < levels
+        if depth > 1:
+            assert np.all(np.diff(O.BSP(X, depth, sign_mode=sign_mode, dot_mode=dot_mode).leaves()[0]) > 0)
+    print("%s: refused with %d (%s) at levels = %d; the oracle's first empty node is node %d at depth %d"
+          % (name, status, text, levels, node, depth))
