@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -297,6 +297,44 @@ int  pmk_query_fetch_multi(pmk_query *q, double *Yq, int64_t ldyq, double *Vq);
  * variance (no triangular solve at all): R = 1 without Vq is the mean-only prediction */
 int  pmk_predict_mixture_multi(pmk_model *m, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th, int64_t Nq,
                                const double *Xq, double radius, double delta, double *Yq, int64_t ldyq, double *Vq);
+
+/* ---- kriging with a trend: one generalised-least-squares drift per patch, on the multi-output path -------------------
+ * Every fit above is SIMPLE kriging: c = U^-1 y assumes a zero-mean field, so a prediction falls to 0 where the kernel's
+ * support runs out of data.  A trend makes it ordinary kriging (unknown constant mean, q = 1, h = [1]) or universal
+ * kriging with a linear drift (q = 1 + D, h(x) = [1, x_1 .. x_D]).  The coordinates are the RAW coordinates the model
+ * stores, all D of them, uncentred: beta is with respect to raw coordinates.  With H the n x q basis of a patch:
+ *   [C_Y | C_H] = U^-1 [Y | H],  G = H^T C_H,  beta = G^-1 H^T C_Y (q x R),  C = C_Y - C_H beta  (so H^T C = 0)
+ *   query x*:  mu_j = kq^T C[:, j] + h(x*)^T beta_j,   v = v_sk + |L_G^-1 (h(x*) - kq^T C_H)|^2,  G = L_G L_G^T
+ * where v_sk is the variance of pmk_query_items, ALREADY clamped at its floor (1e-12): the trend term is added after the
+ * clamp.  One beta per patch; the mixture blends the per-patch (mu, v) as before.
+ * The trend is state of the MULTI-OUTPUT path only: pmk_model_fit's c, pmk_query_items, pmk_predict_mixture,
+ * pmk_model_evidence and pmk_model_get_loo ignore it and keep their bits; a single target with a trend is R = 1 here.  It
+ * works on whatever factor is resident (pmk_model_fit, pmk_model_fit_patches, pmk_model_load; diagonal addends; split
+ * mode; fp64 and fp32) and needs R + q <= PMK_MAX_OUTPUTS.  Not available through the sharded / all-gather exchanges.
+ * With a trend set, pmk_model_solve_multi writes H into columns R .. R+q-1 of the target block, solves all R + q columns
+ * in its one launch and runs the per-patch GLS (-3 if R + q > PMK_MAX_OUTPUTS); pmk_model_get_weights_multi then returns
+ * the universal-kriging weights C; pmk_query_items_multi / _fitted return mu and v as above; pmk_model_get_loo_multi
+ * returns res_ij = C_ij / Q_ii and var_i = 1 / Q_ii with Q_ii = d_i - |L_G^-1 C_H[i,:]^T|^2 (the leave-one-out of the
+ * universal-kriging predictor, beta refitted without point i); pmk_model_evidence_multi's quad = Y^T C is the GLS
+ * quadratic form (y - H beta)^T U^-1 (y - H beta) without any change (H^T C = 0), and log det G for a restricted
+ * likelihood comes from pmk_model_get_trend.  Back at PMK_TREND_NONE the next solve clears the extra columns and every
+ * result is bit-identical to a model that never had a trend.  Stage timers "trend_gls" and "trend_items".
+ * Per-patch status tinfo[r]: 0 ok; a in 1..q: pivot a of the Cholesky of G_r is <= 0 or NaN (a basis column that is
+ * exactly zero or exactly dependent, e.g. a coordinate that is 0 for every point); n_r + 1: the patch has n_r < q points
+ * (flagged without computing; n_r + 1 <= q then, so a value in 1..q means this whenever n_r < q and a pivot otherwise:
+ * tell the two apart by n_r).  A flagged patch, and a patch whose factorisation failed (pmk_model_info != 0; its tinfo
+ * stays 0), gets NaN in beta, in its R weight columns and in everything derived from them; other patches keep their bits.
+ * A NEARLY singular G (points that are almost collinear in an oblique direction) is NOT flagged: G is returned so that
+ * the caller can judge its conditioning. */
+enum { PMK_TREND_NONE = -1, PMK_TREND_CONSTANT = 0, PMK_TREND_LINEAR = 1 };
+/* host state only; marks the multi-output weights stale (run pmk_model_solve_multi again).  -2: unknown degree */
+int  pmk_model_set_trend(pmk_model *m, int degree);
+/* blocks. *q: basis functions of the last solve (0 without a trend); beta[a + q*(j + R*r)]: coefficient a of column j of
+ * patch r; G[a + q*(b + q*r)] = (H^T U^-1 H)_ab of patch r.  Any pointer may be NULL.  -3 before pmk_model_solve_multi. */
+int  pmk_model_get_trend(pmk_model *m, int *q, double *beta, double *G);
+/* blocks. tinfo[P] as above (zeros without a trend); returns 1 if any patch is flagged, 0 if none, -3 before
+ * pmk_model_solve_multi */
+int  pmk_model_trend_info(pmk_model *m, int32_t *tinfo);
 
 /* ---- model selection from the resident factor -------------------------------------------------------------------------
  * Two per-patch scores of a fit at (theta, sigma2), both from what pmk_model_fit leaves on the device (Rasmussen &

@@ -20,6 +20,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        setuppartition, getpartitionlines!, organizetrainingsets, fetchhyperplanes,
        MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
+       settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates
 
 # ------------------------------------------------------------------------------------------ errors
@@ -407,6 +408,8 @@ mutable struct MixtureGPType{T}           # mixtureGP.jl:38-52 (+ the device mod
     handle::Ref{Ptr{Cvoid}}     # the same handle, shared with U_set / L_set
     θ_set::Vector{Any}          # the kernel of every patch after fitmixtureGP!(η, y_parts, θs, σ²s); empty otherwise
     N_global::Int               # > 0: built by MixtureGPType(root, X, ε) from N_global points; the model is resident
+    R_multi::Int                # target columns the model holds (fitmixtureGPmulti!): the library writes this many, so the
+                                # wrappers that size output arrays from a caller's R refuse any other value
 end
 function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{HyperplaneType{T}}) where T
     N = length(X_parts)
@@ -415,7 +418,7 @@ function MixtureGPType(X_parts::Vector{Vector{Vector{T}}}, hps::Vector{Hyperplan
     η = MixtureGPType{T}(X_parts, Vector{Vector{T}}(undef, N), Vector{T}(undef, N),
                          LazyFactors{T,Matrix{T}}(h, 2, n, Dict{Int,Matrix{T}}()),
                          LazyFactors{T,LowerTriangular{T,Matrix{T}}}(h, 1, n, Dict{Int,LowerTriangular{T,Matrix{T}}}()),
-                         hps, C_NULL, h, Any[], 0)
+                         hps, C_NULL, h, Any[], 0, 0)
     finalizer(e -> (e.model != C_NULL && ccall((:pmk_model_destroy, libpmk), Cvoid, (Ptr{Cvoid},), e.model); nothing), η)
     return η
 end
@@ -593,6 +596,7 @@ function fitmixtureGPmulti!(η::MixtureGPType{T}, Y_parts::Vector{Matrix{T}}, θ
         check(ccall((:pmk_model_set_targets_multi, libpmk), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Float64}}, Ptr{Int64}),
                     η.model, R, [pointer(Y) for Y in Ys], ldy), "pmk_model_set_targets_multi")
     end
+    η.R_multi = R
     check(ccall((:pmk_model_solve_multi, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_solve_multi")
     Cs = [Matrix{Float64}(undef, size(Y, 1), R) for Y in Ys]
     GC.@preserve Cs check(ccall((:pmk_model_get_weights_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}),
@@ -682,6 +686,57 @@ function loomixtureGPmulti(η::MixtureGPType{T}, R::Integer) where T
                                      (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
                                      η.model, [pointer(A) for A in RES], ldres, [pointer(a) for a in var]), "pmk_model_get_loo_multi")
     return [A[:, 1:R] for A in RES], var
+end
+
+# ------------------------------------------------------------------------------------------ kriging with a trend
+# One generalised-least-squares drift per patch on the multi-output path (include/pmk.h): :none is simple kriging (the
+# default), :constant ordinary kriging (h = [1]), :linear universal kriging with h(x) = [1, x₁ … x_D] in the raw, uncentred
+# coordinates.  The single-output calls ignore it.
+"""settrendmixtureGP!(η, R, trend) -> C_set: set the trend of the fitted η (:none, :constant or :linear) and solve the R
+target columns of fitmixtureGPmulti! again from the resident factor; returns the n_r x R weights (the universal-kriging
+weights with a trend).  querymixtureGPmulti!, logevidencemixtureGPmulti and loomixtureGPmulti then serve unchanged.
+Throws if R + q > 16 or if a patch is flagged (trendinfomixtureGP)."""
+function settrendmixtureGP!(η::MixtureGPType{T}, R::Integer, trend::Symbol) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before settrendmixtureGP!"))
+    trend in (:none, :constant, :linear) || throw(ArgumentError("trend must be :none, :constant or :linear"))
+    R == η.R_multi || throw(ArgumentError("R = $R, but fitmixtureGPmulti! set $(η.R_multi) target columns"))
+    degree = trend === :none ? -1 : trend === :constant ? 0 : 1
+    check(ccall((:pmk_model_set_trend, libpmk), Cint, (Ptr{Cvoid}, Cint), η.model, degree), "pmk_model_set_trend")
+    check(ccall((:pmk_model_solve_multi, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_solve_multi")
+    flags = trendinfomixtureGP(η)
+    any(flags .!= 0) && throw(PMKError("the trend basis of patch $(findfirst(flags .!= 0)) is rank deficient"))
+    Cs = [Matrix{Float64}(undef, length(X), R) for X in η.X_parts]
+    ldc = Int64[size(c, 1) for c in Cs]
+    GC.@preserve Cs check(ccall((:pmk_model_get_weights_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}),
+                                η.model, [pointer(c) for c in Cs], ldc), "pmk_model_get_weights_multi")
+    return Cs
+end
+
+"""trendmixtureGP(η, R) -> (β_set, G_set): β_set[r] is q x R (coefficients of [1, x₁ … x_D] for every target column of
+patch r), G_set[r] = HᵀU⁻¹H (q x q; its conditioning is the caller's to judge, log det G enters a restricted likelihood).
+q = 0 without a trend."""
+function trendmixtureGP(η::MixtureGPType{T}, R::Integer) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before trendmixtureGP"))
+    R == η.R_multi || throw(ArgumentError("R = $R, but fitmixtureGPmulti! set $(η.R_multi) target columns"))
+    P = length(η.X_parts)
+    q = Ref{Cint}(0)
+    check(ccall((:pmk_model_get_trend, libpmk), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}), η.model, q,
+                Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL)), "pmk_model_get_trend")
+    nq = Int(q[])
+    β = Array{Float64}(undef, nq, R, P); G = Array{Float64}(undef, nq, nq, P)
+    nq > 0 && check(ccall((:pmk_model_get_trend, libpmk), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}), η.model, q,
+                          β, G), "pmk_model_get_trend")
+    return [β[:, :, r] for r = 1:P], [G[:, :, r] for r = 1:P]
+end
+
+"""trendinfomixtureGP(η) -> Vector{Int32} of the P per-patch flags: 0 ok, a in 1..q: pivot a of the Cholesky of G failed,
+n_r + 1: the patch has fewer points than basis functions"""
+function trendinfomixtureGP(η::MixtureGPType{T}) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before trendinfomixtureGP"))
+    flags = Vector{Int32}(undef, length(η.X_parts))
+    rc = ccall((:pmk_model_trend_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), η.model, flags)
+    rc < 0 && check(rc, "pmk_model_trend_info")
+    return flags
 end
 
 # ------------------------------------------------------------------------------------------ per-patch kernels and noise

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pmk_model_loo": (C.c_int, [_vp]),
     "pmk_model_get_loo": (C.c_int, [_vp, _dpp, _dpp]),
     "pmk_model_get_loo_multi": (C.c_int, [_vp, _dpp, _ip, _dpp]),
+    "pmk_model_set_trend": (C.c_int, [_vp, C.c_int]),
+    "pmk_model_get_trend": (C.c_int, [_vp, C.POINTER(C.c_int), _dp, _dp]),
+    "pmk_model_trend_info": (C.c_int, [_vp, _i32p]),
     "pmk_model_fit_patches": (C.c_int, [_vp, _kp, _dp]),
     "pmk_model_set_kernels": (C.c_int, [_vp, _kp]),
     "pmk_model_get_hyper": (C.c_int, [_vp, _kp, _dp]),

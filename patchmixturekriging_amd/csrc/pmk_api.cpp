@@ -475,6 +475,7 @@ void pmk_model_destroy(pmk_model *m)
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
     dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt); dev_free(m->d_ths); dev_free(m->d_sigma2s);
     dev_free(m->d_pidx_off); dev_free(m->d_pidx); dev_free(m->d_gchunk); dev_free(m->d_gstage);
+    dev_free(m->d_tbeta); dev_free(m->d_tL); dev_free(m->d_tG); dev_free(m->d_tinfo);
     for (void **p : {&m->d_diag, &m->d_x, &m->d_y, &m->d_z, &m->d_c, &m->d_a, &m->d_inv, &m->d_strip, &m->d_partial, &m->d_solve_part, &m->d_chain,
                      &m->d_ym, &m->d_cm, &m->d_loo_tasks}) {
         if (*p) (void)hipFree(*p);
@@ -786,6 +787,7 @@ int pmk_model_set_targets_multi_global(pmk_model *m, int R, const double *Y, int
     const double *d_src = nullptr;
     if (int rc = global_source(m, Y, (size_t)(ldy * (R - 1) + m->N_global), &d_src)) return rc;
     if (int rc = PMK_BY_DTYPE(m, launch_gather_multi(m, R, d_src, ldy, m->ctx->stream))) return rc;
+    m->trend_cols_dirty = false;        // the whole block was rewritten: columns >= R are zero
     m->R_multi = R;
     return 0;
 }
@@ -1671,8 +1673,15 @@ int pmk_model_set_targets_multi(pmk_model *m, int R, const double *const *Y, con
     m->R_multi = 0;
     m->multi_solved = false;
     if (int rc = upload_real(m, m->d_ym, 0, hy.data(), count)) return rc;
+    m->trend_cols_dirty = false;        // the whole block was rewritten: columns >= R are zero
     m->R_multi = R;
     return 0;
+}
+
+// basis functions of the trend the model is set to: 0, 1 or 1 + D
+static int trend_q_of(const pmk_model *m)
+{
+    return m->trend_degree == PMK_TREND_CONSTANT ? 1 : m->trend_degree == PMK_TREND_LINEAR ? 1 + m->D : 0;
 }
 
 int pmk_model_solve_multi(pmk_model *m)
@@ -1683,13 +1692,88 @@ int pmk_model_solve_multi(pmk_model *m)
         return -2;
     }
     if (m->R_multi < 1) { set_error("pmk_model_solve_multi: no multi-output targets (pmk_model_set_targets_multi)"); return -3; }
+    const int R = m->R_multi, qt = trend_q_of(m);
+    if (R + qt > PMK_MAX_OUTPUTS) {
+        set_error("pmk_model_solve_multi: R=%d target columns and q=%d trend columns exceed %d", R, qt, PMK_MAX_OUTPUTS);
+        return -3;
+    }
     pmk_ctx *c = m->ctx;
     PMK_HIP(hipSetDevice(c->device));
+    m->multi_solved = false;
+    if (qt > 0 && !m->d_tbeta) {
+        if (dev_alloc(&m->d_tbeta, m->P * 5 * PMK_MAX_OUTPUTS) || dev_alloc(&m->d_tL, m->P * 25) ||
+            dev_alloc(&m->d_tG, m->P * 25) || dev_alloc(&m->d_tinfo, m->P))
+            return -100;
+    }
     c->tic("solve_multi");
-    const int rc = PMK_BY_DTYPE(m, launch_solve_multi(m, c->stream));
+    int rc = 0;
+    // H into columns R .. R+q-1 of Y; with the trend back at none, one fill with q = 0 clears what an earlier solve left
+    if (qt > 0 || m->trend_cols_dirty) {
+        rc = PMK_BY_DTYPE(m, launch_trend_fill(m, R, qt, c->stream));
+        if (!rc) m->trend_cols_dirty = qt > 0;
+    }
+    if (!rc) rc = PMK_BY_DTYPE(m, launch_solve_multi(m, c->stream));
     c->toc("solve_multi");
     if (rc) return rc;
+    if (qt > 0) {
+        c->tic("trend_gls");
+        rc = PMK_BY_DTYPE(m, launch_trend_gls(m, R, qt, c->stream));
+        c->toc("trend_gls");
+        if (rc) return rc;
+    }
+    m->trend_q = qt;
     m->multi_solved = true;
+    return 0;
+}
+
+int pmk_model_set_trend(pmk_model *m, int degree)
+{
+    if (!m) { set_error("pmk_model_set_trend: model is NULL"); return -1; }
+    if (degree != PMK_TREND_NONE && degree != PMK_TREND_CONSTANT && degree != PMK_TREND_LINEAR) {
+        set_error("pmk_model_set_trend: unknown degree %d (PMK_TREND_NONE, _CONSTANT or _LINEAR)", degree);
+        return -2;
+    }
+    m->trend_degree = degree;
+    m->multi_solved = false;            // the resident weights belong to the previous trend
+    return 0;
+}
+
+int pmk_model_get_trend(pmk_model *m, int *q, double *beta, double *G)
+{
+    if (!m) { set_error("pmk_model_get_trend: model is NULL"); return -1; }
+    if (!m->multi_solved) { set_error("pmk_model_get_trend: pmk_model_solve_multi has not run"); return -3; }
+    const int qt = m->trend_q, R = m->R_multi;
+    if (q) *q = qt;
+    if (qt == 0 || (!beta && !G)) return 0;
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    std::vector<double> hb((size_t)m->P * 5 * PMK_MAX_OUTPUTS), hg((size_t)m->P * 25);
+    if (beta) PMK_HIP(hipMemcpyAsync(hb.data(), m->d_tbeta, sizeof(double) * hb.size(), hipMemcpyDeviceToHost, m->ctx->stream));
+    if (G) PMK_HIP(hipMemcpyAsync(hg.data(), m->d_tG, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, m->ctx->stream));
+    PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+    for (int64_t r = 0; r < m->P; ++r) {
+        if (beta)
+            for (int j = 0; j < R; ++j)
+                for (int a = 0; a < qt; ++a) beta[a + qt * (j + (int64_t)R * r)] = hb[(size_t)((r * PMK_MAX_OUTPUTS + j) * 5 + a)];
+        if (G)
+            for (int b = 0; b < qt; ++b)
+                for (int a = 0; a < qt; ++a) G[a + qt * (b + (int64_t)qt * r)] = hg[(size_t)(r * 25 + a + 5 * b)];
+    }
+    return 0;
+}
+
+int pmk_model_trend_info(pmk_model *m, int32_t *tinfo)
+{
+    if (!m || !tinfo) { set_error("pmk_model_trend_info: NULL argument"); return -1; }
+    if (!m->multi_solved) { set_error("pmk_model_trend_info: pmk_model_solve_multi has not run"); return -3; }
+    if (m->trend_q == 0) {
+        for (int64_t r = 0; r < m->P; ++r) tinfo[r] = 0;
+        return 0;
+    }
+    PMK_HIP(hipSetDevice(m->ctx->device));
+    PMK_HIP(hipMemcpyAsync(tinfo, m->d_tinfo, sizeof(int32_t) * (size_t)m->P, hipMemcpyDeviceToHost, m->ctx->stream));
+    PMK_HIP(hipStreamSynchronize(m->ctx->stream));
+    for (int64_t r = 0; r < m->P; ++r)
+        if (tinfo[r] != 0) return 1;
     return 0;
 }
 
@@ -1729,7 +1813,7 @@ static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_
     pmk_ctx *c = m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int R = m->R_multi;
+    const int R = m->R_multi, qt = m->trend_q;      // with a trend the items kernel also emits kq . C_H: R + q columns
     q->R_items = 0;
     q->mixed_multi = false;
     // chunks of 16 items per region (item_means_kernel): prefix over the regions
@@ -1744,19 +1828,26 @@ static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_
         if (dev_alloc(&q->d_mcpre, m->P + 1)) return -100;
         q->mcpre_cap = m->P + 1;
     }
-    if (q->um_cap < q->total * R) {
+    if (q->um_cap < q->total * (R + qt)) {
         dev_free(q->d_um);
         q->um_cap = 0;
-        if (dev_alloc(&q->d_um, q->total * R)) return -100;
-        q->um_cap = q->total * R;
+        if (dev_alloc(&q->d_um, q->total * (R + qt))) return -100;
+        q->um_cap = q->total * (R + qt);
     }
     PMK_HIP(hipMemcpyAsync(q->d_mcpre, q->mcpre.data(), sizeof(int64_t) * q->mcpre.size(), hipMemcpyHostToDevice, s));
     q->R_items = R;
+    q->um_ld = R + qt;
     c->tic("items_multi");
     int rc = th ? PMK_BY_DTYPE(m, launch_items_multi(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_multi_patches(q, s));
     // v exactly as pmk_query_items / pmk_query_items_fitted (u ignored)
     if (!rc && want_var) rc = th ? PMK_BY_DTYPE(m, launch_items(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_patches(q, s));
     c->toc("items_multi");
+    // mu += h^T beta and, after the clamp of v at min_v, v += |L_G^-1 (h - kq . C_H)|^2
+    if (!rc && qt > 0) {
+        c->tic("trend_items");
+        rc = launch_trend_items(q, R, qt, want_var != 0, s);
+        c->toc("trend_items");
+    }
     if (rc) { q->R_items = 0; return rc; }
     q->var_items = want_var != 0;
     return 0;
@@ -1957,7 +2048,9 @@ static int loo_values_common(pmk_model *m, int R, std::vector<double> *res, std:
     const int64_t rp = R ? PMK_MAX_OUTPUTS : 1, ny = std::max<int64_t>(m->tot_y, 1);
     DevTmp<double> dr, dv;
     if ((res && dr.alloc(ny * rp)) || (var && dv.alloc(ny))) return -100;
-    if (int rc = PMK_BY_DTYPE(m, launch_loo_values(m, R, dr, dv, c->stream))) return rc;
+    if (R && m->trend_q > 0) {
+        if (int rc = PMK_BY_DTYPE(m, launch_trend_loo_values(m, R, m->trend_q, dr, dv, c->stream))) return rc;
+    } else if (int rc = PMK_BY_DTYPE(m, launch_loo_values(m, R, dr, dv, c->stream))) return rc;
     if (res) {
         res->resize((size_t)(ny * rp));
         PMK_HIP(hipMemcpyAsync(res->data(), dr, sizeof(double) * res->size(), hipMemcpyDeviceToHost, c->stream));

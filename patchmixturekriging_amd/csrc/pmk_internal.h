@@ -144,6 +144,13 @@ struct pmk_model {
     void *d_ym = nullptr;               // targets Y
     void *d_cm = nullptr;               // weights C (the forward solve's Z in between)
     bool multi_solved = false;
+    // trend of the multi-output path (pmk_trend.hip): the degree asked for, the q the resident weights were solved with,
+    // whether columns >= R of the target block still hold an earlier solve's basis, and the per-patch GLS state (double)
+    int trend_degree = PMK_TREND_NONE;
+    int trend_q = 0;
+    bool trend_cols_dirty = false;
+    double *d_tbeta = nullptr, *d_tL = nullptr, *d_tG = nullptr;   // P x 80, P x 25, P x 25 (layouts in pmk_trend.hip)
+    int32_t *d_tinfo = nullptr;                                    // P
     // model selection from the resident factor (pmk_loo.hip): d = diag((L L^T)^-1), always double, yoff addressing;
     // valid from pmk_model_loo until the next pmk_model_fit.  The strip tasks depend on the geometry only: built once.
     double *d_dloo = nullptr;
@@ -199,7 +206,8 @@ struct pmk_query {
     // multi-output prediction (pmk_query_items_multi / _mix_multi): R means per item and per query
     int R_items = 0;                    // 0: items_multi has not run on the current plan
     bool var_items = false, mixed_multi = false;
-    double *d_um = nullptr; int64_t um_cap = 0;       // sorted items x R (row-major)
+    double *d_um = nullptr; int64_t um_cap = 0;       // sorted items x um_ld (row-major)
+    int um_ld = 0;                      // R_items + q of the model's trend: the items kernel also emits kq . C_H
     double *d_yqm = nullptr; int64_t yqm_cap = 0;     // Nq x R column-major
     int64_t *d_mcpre = nullptr; int64_t mcpre_cap = 0, mchunks = 0;   // chunks of 16 items per region: prefix [P+1]
     std::vector<int64_t> mcpre;         // host copy (source of the upload)
@@ -231,6 +239,9 @@ namespace pmk {
     int launch_gather_points(const pmk_model *m, const double *d_X, const double *d_y, hipStream_t s);               \
     int launch_gather_vector(const pmk_model *m, const double *d_src, void *d_dst, hipStream_t s);                   \
     int launch_gather_multi(const pmk_model *m, int R, const double *d_Y, int64_t ldy, hipStream_t s);               \
+    int launch_trend_fill(const pmk_model *m, int R, int q, hipStream_t s);                                          \
+    int launch_trend_gls(pmk_model *m, int R, int q, hipStream_t s);                                                 \
+    int launch_trend_loo_values(const pmk_model *m, int R, int q, double *d_res, double *d_var, hipStream_t s);      \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -250,6 +261,7 @@ int launch_plan_fill(pmk_query *q, double radius, double delta, hipStream_t s);
 int launch_sort_items(pmk_query *q, hipStream_t s);
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
+int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);
 int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s);
 int launch_export_results(pmk_query *q, double *u_out, double *v_out, hipStream_t s);

@@ -174,7 +174,8 @@ int launch_solve_multi(pmk_model *m, hipStream_t s)
 // One wave per chunk of (up to) 16 items of one region: lane l evaluates k(xq of item l & 15, x of point k0 + (l >> 4))
 // -- the A operand of the MFMA, query first as in queryinner! (mixtureGP.jl:304) -- and the B operand is row k0 + (l >> 4)
 // of C_r.  Chunk g of the whole list lies in the region r with cpre[r] <= g < cpre[r + 1] (chunks per region, host
-// prefix).  Consecutive chunks share their region's C_r: xcd_remap keeps them on one XCD's L2.
+// prefix).  Consecutive chunks share their region's C_r: xcd_remap keeps them on one XCD's L2.  R is the number of
+// columns emitted and the row length of U: the target columns, plus the q columns of C_H with a trend (pmk_trend.hip).
 // PP = true (pmk_query_items_multi_fitted): theta of the chunk's region from the model's device array; a wave handles one
 // region, so the descriptor is wave-uniform.
 constexpr int IM_THREADS = 256;
@@ -254,11 +255,11 @@ int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s)
         if (s34)                                                                                                         \
             hipLaunchKernelGGL((item_means_kernel<DD, PMK_SPLINE34>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,     \
                                (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->R_items, q->d_um);              \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->um_ld, q->d_um);              \
         else                                                                                                             \
             hipLaunchKernelGGL((item_means_kernel<DD, 0>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,                \
                                (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->R_items, q->d_um);              \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->um_ld, q->d_um);              \
         break;
         PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
 #undef PMK_CASE
@@ -281,11 +282,11 @@ int launch_items_multi_patches(pmk_query *q, hipStream_t s)
         if (m->hyper_s34)                                                                                                \
             hipLaunchKernelGGL((item_means_kernel<DD, PMK_SPLINE34, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc, \
                                (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->R_items, q->d_um); \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->um_ld, q->d_um); \
         else                                                                                                             \
             hipLaunchKernelGGL((item_means_kernel<DD, 0, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,          \
                                (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->R_items, q->d_um); \
+                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->um_ld, q->d_um); \
         break;
         PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
 #undef PMK_CASE
@@ -301,10 +302,11 @@ int launch_items_multi_patches(pmk_query *q, hipStream_t s)
 
 #ifndef PMK_REAL_F32
 // mix_kernel (pmk_kernels.hip) with R means: the same weights (neighbours phi_w(|t|) in hyperplane order, home 1 last,
-// normalised) and, per column, the same order of operations as its Yq.  Yq is Nq x R column-major (ld Nq).
+// normalised) and, per column, the same order of operations as its Yq.  Yq is Nq x R column-major (ld Nq).  A row of U
+// has ldu >= R columns (ldu > R with a trend, pmk_trend.hip: the extra columns are not mixed).
 __global__ __launch_bounds__(256) void mix_multi_kernel(int64_t q0, int64_t q1, int64_t Nq, const int64_t *__restrict__ qoff,
                                                         const double *__restrict__ item_t, const int32_t *__restrict__ item_pos,
-                                                        const double *__restrict__ U, int R, pmk_kernel_desc wth,
+                                                        const double *__restrict__ U, int ldu, int R, pmk_kernel_desc wth,
                                                         double *__restrict__ yq)
 {
     const int64_t j = q0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -319,7 +321,7 @@ __global__ __launch_bounds__(256) void mix_multi_kernel(int64_t q0, int64_t q1, 
         double y = 0.0;
         for (int64_t it = b; it < e; ++it) {
             const double w = ((it == e - 1) ? 1.0 : profile(wth, fabs(item_t[it]))) / sw;
-            const double ui = U[(int64_t)item_pos[it] * R + col];
+            const double ui = U[(int64_t)item_pos[it] * ldu + col];
             y = (it == b) ? w * ui : y + w * ui;
         }
         yq[col * Nq + j] = y;
@@ -330,7 +332,7 @@ int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64
 {
     if (q1 <= q0) return 0;
     hipLaunchKernelGGL(mix_multi_kernel, dim3((unsigned)((q1 - q0 + 255) / 256)), dim3(256), 0, s, q0, q1, q->Nq, q->d_qoff,
-                       q->d_item_t, q->d_item_pos, q->d_um, q->R_items, wth, q->d_yqm);
+                       q->d_item_t, q->d_item_pos, q->d_um, q->um_ld, q->R_items, wth, q->d_yqm);
     PMK_HIP(hipGetLastError());
     return 0;
 }

@@ -33,6 +33,9 @@ static int no_gpu(const char *what)
     int launch_gather_points(const pmk_model *, const double *, const double *, hipStream_t) { return no_gpu("launch_gather_points"); } \
     int launch_gather_vector(const pmk_model *, const double *, void *, hipStream_t) { return no_gpu("launch_gather_vector"); } \
     int launch_gather_multi(const pmk_model *, int, const double *, int64_t, hipStream_t) { return no_gpu("launch_gather_multi"); } \
+    int launch_trend_fill(const pmk_model *, int, int, hipStream_t) { return no_gpu("launch_trend_fill"); }         \
+    int launch_trend_gls(pmk_model *, int, int, hipStream_t) { return no_gpu("launch_trend_gls"); }                 \
+    int launch_trend_loo_values(const pmk_model *, int, int, double *, double *, hipStream_t) { return no_gpu("launch_trend_loo_values"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -46,6 +49,7 @@ int launch_plan_fill(pmk_query *, double, double, hipStream_t) { return no_gpu("
 int launch_sort_items(pmk_query *, hipStream_t) { return no_gpu("launch_sort_items"); }
 int launch_mix(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix"); }
 int launch_mix_multi(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_multi"); }
+int launch_trend_items(pmk_query *, int, int, bool, hipStream_t) { return no_gpu("launch_trend_items"); }
 int launch_export_requests(pmk_query *, int64_t, int64_t, double *, int32_t *, hipStream_t) { return no_gpu("launch_export_requests"); }
 int launch_export_request_diag(pmk_query *, int64_t, int64_t, double *, hipStream_t) { return no_gpu("launch_export_request_diag"); }
 int launch_export_results(pmk_query *, double *, double *, hipStream_t) { return no_gpu("launch_export_results"); }

@@ -377,6 +377,34 @@ class DeviceModel:
                    "pmk_model_get_weights_multi")
         return out
 
+    # ---- kriging with a trend: one GLS drift per patch on the multi-output path (include/pmk.h)
+    def set_trend(self, trend):
+        """pmk_model_set_trend: "none" / None (simple kriging), "constant" (ordinary kriging, h = [1]) or "linear" (universal
+        kriging, h(x) = [1, x_1 .. x_D] in the raw coordinates).  Host state only: the multi-output weights become stale,
+        run solve_multi again."""
+        _lib.check(self.ctx.L.pmk_model_set_trend(self.h, trend_degree(trend)), "pmk_model_set_trend")
+        self._multi_solved = False
+
+    def trend(self):
+        """pmk_model_get_trend -> (beta_set, G_set) of the last solve_multi: beta_set[r] is q x R (coefficients of
+        [1, x_1 .. x_D] per target column), G_set[r] = H^T U^-1 H (q x q).  q = 0 without a trend."""
+        self._need(multi=True)
+        q = C.c_int(0)
+        _lib.check(self.ctx.L.pmk_model_get_trend(self.h, C.byref(q), None, None), "pmk_model_get_trend")
+        q = int(q.value)
+        beta, G = np.zeros((self.P, self.R, q)), np.zeros((self.P, q, q))
+        if q:
+            _lib.check(self.ctx.L.pmk_model_get_trend(self.h, None, _d(beta), _d(G)), "pmk_model_get_trend")
+        return [beta[r].T.copy() for r in range(self.P)], [G[r].T.copy() for r in range(self.P)]
+
+    def trend_info(self):
+        """pmk_model_trend_info -> int32 [P]: 0 ok; a in 1..q: pivot a of the Cholesky of G_r is <= 0 or NaN; n_r + 1: the
+        patch has fewer points than basis functions"""
+        self._need(multi=True)
+        flags = np.zeros(self.P, dtype=np.int32)
+        _lib.check(self.ctx.L.pmk_model_trend_info(self.h, flags.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_model_trend_info")
+        return flags
+
     # ---- model selection from the resident factor (per patch: a point of several overlapping patches has a score in each)
     def _need(self, factor=True, loo=False, multi=False, targets=False):
         if factor and not self._has_factor:
@@ -661,6 +689,35 @@ def multi_targets(Y_parts, n):
     return Ys
 
 
+TREND_DEGREES = {None: -1, "none": -1, "constant": 0, "linear": 1}      # PMK_TREND_NONE / _CONSTANT / _LINEAR
+
+
+def trend_degree(trend):
+    """the PMK_TREND_* value of a trend name (ValueError for an unknown one, before any device call)"""
+    if not isinstance(trend, (str, type(None))) or trend not in TREND_DEGREES:
+        raise ValueError("trend must be 'none', 'constant' or 'linear', got %r" % (trend,))
+    return TREND_DEGREES[trend]
+
+
+def trend_columns(trend, D, R):
+    """q of a trend on D coordinates, checked against the R target columns: R + q <= MAX_OUTPUTS (the basis shares the
+    16-column blocks of the multi-output solve with the targets)"""
+    q = {-1: 0, 0: 1, 1: 1 + int(D)}[trend_degree(trend)]
+    if R + q > MAX_OUTPUTS:
+        raise ValueError("R = %d target columns and q = %d trend columns exceed %d" % (R, q, MAX_OUTPUTS))
+    return q
+
+
+class TrendRankException(np.linalg.LinAlgError):
+    """the trend basis of a patch is rank deficient (DeviceModel.trend_info)"""
+
+    def __init__(self, patch, flag):
+        super().__init__("patch %d: the trend basis is rank deficient (flag %d: a pivot of H^T U^-1 H, or n + 1 for a "
+                         "patch with fewer points than basis functions)" % (patch, flag))
+        self.patch = patch
+        self.flag = flag
+
+
 def patch_hyper(thetas, sigma2s, P):
     """validate per-patch hyperparameters before any device call -> (pmk_kernel_desc[P], float64 [P] or None).
     ValueError for a wrong length; TypeError for a closure-carrying kernel (anything with a diag_addend, or whose
@@ -873,6 +930,7 @@ def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
     """fitmixtureGP! (mixtureGP.jl:70-118) with R target columns per patch that share one factor: the fit runs once on
     column 0 (c_set, L_set as fitmixtureGP_ leaves them), then every column is solved from the resident factor
     (c = U \\ y of mixtureGP.jl:106 for R right-hand sides).  Stores eta.C_set (a list of n_r x R)."""
+    eta.beta_set = None             # the coefficients of an earlier fitmixtureGP_trend_ do not belong to this fit
     if getattr(eta, "_from_tree", False):
         # Y_parts is the GLOBAL (N, R) column-major array; its first column is N contiguous values
         _refuse_closure_kernel(theta, "fitmixtureGP_multi_")
@@ -882,6 +940,7 @@ def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
         col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
         fitmixtureGP_(eta, col0, theta, sigma2)
         model.set_targets_multi_global(Y_parts)
+        model.set_trend(None)           # the resident model may carry the trend of an earlier fitmixtureGP_trend_
         model.solve_multi()
         eta.C_set = model.weights_multi()
         return eta
@@ -891,6 +950,40 @@ def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
     model.set_targets_multi(Ys)
     model.solve_multi()
     eta.C_set = model.weights_multi()
+    return eta
+
+
+def fitmixtureGP_trend_(eta, Y_parts, theta, sigma2, trend="constant"):
+    """fitmixtureGP_multi_ with a trend: ordinary ("constant", h = [1]) or universal ("linear", h(x) = [1, x_1 .. x_D] in
+    the raw coordinates) kriging with one generalised-least-squares drift per patch.  Y_parts as for fitmixtureGP_multi_
+    (vectors or n_r x R columns; the GLOBAL (N,) or (N, R) array on an eta built by from_tree); R + q <= 16.  Runs fit ->
+    multi-output targets -> trend -> solve and stores eta.C_set (the universal-kriging weights, n_r x R) and eta.beta_set
+    (q x R per patch).  querymixtureGP_multi / _multi_patches, logevidencemixtureGP_multi (its quadratic form is then the
+    GLS one) and loomixtureGP_multi serve unchanged.  Raises TrendRankException for a flagged patch."""
+    trend_degree(trend)
+    _refuse_closure_kernel(theta, "fitmixtureGP_trend_")     # a warp-feature model has more coordinates than positions
+    if getattr(eta, "_from_tree", False):
+        model = eta._tree_model
+        ya = GlobalArray(Y_parts, "Y")
+        R, _ = ya.columns(model.N)
+        trend_columns(trend, model.D, R)
+        col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
+        fitmixtureGP_(eta, col0, theta, sigma2)
+        model.set_targets_multi_global(Y_parts)
+    else:
+        Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
+        trend_columns(trend, eta.X_parts[0].shape[1], Ys[0].shape[1])
+        fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
+        model = eta._model
+        model.set_targets_multi(Ys)
+    model.set_trend(trend)
+    model.solve_multi()
+    flags = model.trend_info()
+    bad = np.nonzero(flags)[0]
+    if len(bad):
+        raise TrendRankException(int(bad[0]), int(flags[bad[0]]))
+    eta.C_set = model.weights_multi()
+    eta.beta_set = model.trend()[0]
     return eta
 
 
