@@ -862,6 +862,28 @@ int pmk_test_model_packed(pmk_model *m, int64_t patch, int what, int64_t *ld, do
     return download_real_2d(m, out, count, src, off, count, count, 1, m->ctx->stream);
 }
 
+// the theta the launchers take for the model's own hyperparameters: one descriptor after a plain fit, else null for the
+// per-patch device arrays
+static const pmk_kernel_desc *fitted_theta(const pmk_model *m) { return m->hyper_uniform ? &m->th : nullptr; }
+
+// The three timed stages of a fit: kernel matrix (th as the launchers take it, m->fuse_k1 decided by the caller),
+// factorisation, solve.  The "fit" timer around them and the fitted flag stay with the caller.
+static int fit_stages(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
+{
+    pmk_ctx *c = m->ctx;
+    int rc;
+    c->tic("kernel_matrix");
+    if ((rc = PMK_BY_DTYPE(m, launch_kernel_matrix_slabs(m, th, sigma2, c->stream, 0, m->P, m->fuse_k1)))) return rc;
+    c->toc("kernel_matrix");
+    c->tic("cholesky");
+    if ((rc = PMK_BY_DTYPE(m, launch_cholesky(m, c->stream, 0, m->P)))) return rc;
+    c->toc("cholesky");
+    c->tic("solve");
+    if ((rc = PMK_BY_DTYPE(m, launch_backsolve(m, c->stream, 0, m->P)))) return rc;
+    c->toc("solve");
+    return 0;
+}
+
 int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
 {
     if (!m) { set_error("pmk_model_fit: model is NULL"); return -1; }
@@ -877,7 +899,6 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     m->multi_solved = false;            // a new factor: the multi-output weights are stale
     m->loo_valid = false;               // ... and so is diag((L L^T)^-1)
     m->loaded = false;
-    int rc;
     c->tic("fit");
     // Fused kernel-matrix build (PMK_FUSE_K1=0 turns it off): for the compact Spline34 profile in 2 or 3 dimensions K1
     // writes the diagonal 128 x 128 tiles only, and the factorisation's step launches evaluate every tile below them at
@@ -885,15 +906,7 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     const char *fe = std::getenv("PMK_FUSE_K1");
     const bool fuse_env = !(fe && std::atoi(fe) == 0);
     m->fuse_k1 = fuse_env && th->family == PMK_SPLINE34 && (m->D == 2 || m->D == 3) && !m->split_mode && m->max_nt >= 2;
-    c->tic("kernel_matrix");
-    if ((rc = PMK_BY_DTYPE(m, launch_kernel_matrix_slabs(m, *th, sigma2, c->stream, 0, m->P, m->fuse_k1)))) return rc;
-    c->toc("kernel_matrix");
-    c->tic("cholesky");
-    if ((rc = PMK_BY_DTYPE(m, launch_cholesky(m, c->stream, 0, m->P)))) return rc;
-    c->toc("cholesky");
-    c->tic("solve");
-    if ((rc = PMK_BY_DTYPE(m, launch_backsolve(m, c->stream, 0, m->P)))) return rc;
-    c->toc("solve");
+    if (int rc = fit_stages(m, th, sigma2)) return rc;
     c->toc("fit");
     m->fitted = true;
     return 0;
@@ -944,15 +957,7 @@ int pmk_model_fit_patches(pmk_model *m, const pmk_kernel_desc *ths, const double
     c->tic("fit");
     // always the whole lower triangle: the fused build evaluates tiles inside the factorisation, which knows one theta
     m->fuse_k1 = false;
-    c->tic("kernel_matrix");
-    if ((rc = PMK_BY_DTYPE(m, launch_kernel_matrix_slabs_patches(m, c->stream, 0, m->P)))) return rc;
-    c->toc("kernel_matrix");
-    c->tic("cholesky");
-    if ((rc = PMK_BY_DTYPE(m, launch_cholesky(m, c->stream, 0, m->P)))) return rc;
-    c->toc("cholesky");
-    c->tic("solve");
-    if ((rc = PMK_BY_DTYPE(m, launch_backsolve(m, c->stream, 0, m->P)))) return rc;
-    c->toc("solve");
+    if ((rc = fit_stages(m, nullptr, 0.0))) return rc;
     c->toc("fit");
     m->fitted = true;
     return 0;
@@ -1185,7 +1190,7 @@ int pmk_model_queryinner_ex(pmk_model *m, int64_t patch, const pmk_kernel_desc *
         if (hipMemcpyAsync(q.d_xq, Xq, sizeof(double) * (size_t)(Nq * m->D), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -100;
         if (!rc) rc = launch_iota(q.d_sorted_item, Nq, c->stream);
         if (!rc) rc = PMK_BY_DTYPE(m, build_strip_tasks(&q, c->stream));
-        if (!rc) rc = PMK_BY_DTYPE(m, launch_items(&q, *th, c->stream));
+        if (!rc) rc = PMK_BY_DTYPE(m, launch_items(&q, th, c->stream));
         if (!rc && (hipMemcpyAsync(mu, q.d_u, sizeof(double) * (size_t)Nq, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                     hipMemcpyAsync(var, q.d_v, sizeof(double) * (size_t)Nq, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                     hipStreamSynchronize(c->stream) != hipSuccess)) {
@@ -1493,7 +1498,7 @@ int pmk_query_items(pmk_query *q, const pmk_kernel_desc *th)
     pmk_ctx *c = q->m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     c->tic("items");
-    int rc = PMK_BY_DTYPE(q->m, launch_items(q, *th, c->stream));
+    int rc = PMK_BY_DTYPE(q->m, launch_items(q, th, c->stream));
     c->toc("items");
     return rc;
 }
@@ -1507,7 +1512,7 @@ int pmk_query_items_fitted(pmk_query *q)
     pmk_ctx *c = m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     c->tic("items");
-    int rc = m->hyper_uniform ? PMK_BY_DTYPE(m, launch_items(q, m->th, c->stream)) : PMK_BY_DTYPE(m, launch_items_patches(q, c->stream));
+    int rc = PMK_BY_DTYPE(m, launch_items(q, fitted_theta(m), c->stream));
     c->toc("items");
     return rc;
 }
@@ -1838,9 +1843,9 @@ static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_
     q->R_items = R;
     q->um_ld = R + qt;
     c->tic("items_multi");
-    int rc = th ? PMK_BY_DTYPE(m, launch_items_multi(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_multi_patches(q, s));
+    int rc = PMK_BY_DTYPE(m, launch_items_multi(q, th, s));
     // v exactly as pmk_query_items / pmk_query_items_fitted (u ignored)
-    if (!rc && want_var) rc = th ? PMK_BY_DTYPE(m, launch_items(q, *th, s)) : PMK_BY_DTYPE(m, launch_items_patches(q, s));
+    if (!rc && want_var) rc = PMK_BY_DTYPE(m, launch_items(q, th, s));
     c->toc("items_multi");
     // mu += h^T beta and, after the clamp of v at min_v, v += |L_G^-1 (h - kq . C_H)|^2
     if (!rc && qt > 0) {
@@ -1865,7 +1870,7 @@ int pmk_query_items_multi_fitted(pmk_query *q, int want_var)
     if (!q || !q->planned) { set_error("pmk_query_items_multi_fitted: query is not planned"); return -1; }
     pmk_model *m = q->m;
     if (m->ths.empty()) { set_error("pmk_query_items_multi_fitted: the model holds no kernels (pmk_model_set_kernels)"); return -3; }
-    return items_multi_common(q, m->hyper_uniform ? &m->th : nullptr, want_var);
+    return items_multi_common(q, fitted_theta(m), want_var);
 }
 
 int pmk_query_mix_multi(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1)

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "pmk_device.h"
+#include "pmk_dispatch.h"
 
 namespace pmk {
 
@@ -426,13 +427,7 @@ int bsp_assign_device(pmk_ctx *c, const BspArrays &t, int64_t N, const double *X
         if (list_offsets) list_offsets[0] = 0;
         return 0;
     }
-    switch (t.D) {
-    case 1: return assign_levels<1>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
-    case 2: return assign_levels<2>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
-    case 3: return assign_levels<3>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
-    case 4: return assign_levels<4>(c, t, N, X, eps, offsets, inds, list_offsets, lists);
-    default: set_error("pmk_bsp_assign_device: D=%d outside 1..%d", t.D, MAX_D); return -1;
-    }
+    return dispatch_dim(t.D, [&](auto dd) { return assign_levels<dd()>(c, t, N, X, eps, offsets, inds, list_offsets, lists); });
 }
 
 // The patches of a model as one device index list.  eps >= 0: the eps-set of every leaf, exactly the lists of
@@ -458,13 +453,7 @@ int bsp_patch_index_device(pmk_ctx *c, const BspArrays &t, int64_t N, const doub
         *d_X = mem.release(dX);
         return 0;
     }
-    switch (t.D) {
-    case 1: return assign_keep<1>(c, t, N, X, eps, offsets, d_inds, d_X);
-    case 2: return assign_keep<2>(c, t, N, X, eps, offsets, d_inds, d_X);
-    case 3: return assign_keep<3>(c, t, N, X, eps, offsets, d_inds, d_X);
-    case 4: return assign_keep<4>(c, t, N, X, eps, offsets, d_inds, d_X);
-    default: set_error("pmk_model_create_from_bsp: D=%d outside 1..%d", t.D, MAX_D); return -1;
-    }
+    return dispatch_dim(t.D, [&](auto dd) { return assign_keep<dd()>(c, t, N, X, eps, offsets, d_inds, d_X); });
 }
 
 int bsp_build_device(pmk_ctx *c, int D, int64_t N, const double *X, int levels, int sign_mode, int dot_mode, BspArrays &t)
@@ -473,15 +462,7 @@ int bsp_build_device(pmk_ctx *c, int D, int64_t N, const double *X, int levels, 
     t.P = (int64_t)1 << (levels - 1);
     t.v.assign((size_t)((t.P - 1) * D), 0.0);
     t.c.assign((size_t)(t.P - 1), 0.0);
-    int rc;
-    switch (D) {
-    case 1: rc = build_levels<1>(c, N, X, levels, sign_mode, dot_mode, t); break;
-    case 2: rc = build_levels<2>(c, N, X, levels, sign_mode, dot_mode, t); break;
-    case 3: rc = build_levels<3>(c, N, X, levels, sign_mode, dot_mode, t); break;
-    case 4: rc = build_levels<4>(c, N, X, levels, sign_mode, dot_mode, t); break;
-    default: set_error("pmk_bsp_build_device: D=%d outside 1..%d", D, MAX_D); return -1;
-    }
-    if (rc) return rc;
+    if (int rc = dispatch_dim(D, [&](auto dd) { return build_levels<dd()>(c, N, X, levels, sign_mode, dot_mode, t); })) return rc;
     bsp_fill_preorder(t);
     return 0;
 }

@@ -14,6 +14,7 @@
 // Grid: one workgroup per (patch, chunk of 256 rows), located through the prefix over ceil(ld_r / 256) that the model
 // keeps (gchunk): with ragged patches a P x max chunk grid would be mostly idle.  A point's D doubles are contiguous in
 // X (a gather by nature); the SoA writes are coalesced along i.  The traffic is a few MB: nothing here is tuned.
+#include "pmk_dispatch.h"
 #include "pmk_real.h"
 
 namespace pmk {
@@ -98,13 +99,12 @@ int launch_gather_points(const pmk_model *m, const double *d_X, const double *d_
     const dim3 grid((unsigned)m->gchunks), block(GCHUNK);
     real *xs = (real *)m->d_x, *ys = (real *)m->d_y;
     const int P = (int)m->P;
-    switch (m->D) {
-    case 1: hipLaunchKernelGGL(gather_points_kernel<1>, grid, block, 0, s, m->d_desc, m->d_gchunk, P, m->d_pidx_off, m->d_pidx, d_X, d_y, xs, ys); break;
-    case 2: hipLaunchKernelGGL(gather_points_kernel<2>, grid, block, 0, s, m->d_desc, m->d_gchunk, P, m->d_pidx_off, m->d_pidx, d_X, d_y, xs, ys); break;
-    case 3: hipLaunchKernelGGL(gather_points_kernel<3>, grid, block, 0, s, m->d_desc, m->d_gchunk, P, m->d_pidx_off, m->d_pidx, d_X, d_y, xs, ys); break;
-    case 4: hipLaunchKernelGGL(gather_points_kernel<4>, grid, block, 0, s, m->d_desc, m->d_gchunk, P, m->d_pidx_off, m->d_pidx, d_X, d_y, xs, ys); break;
-    default: set_error("launch_gather_points: D=%d outside 1..%d", m->D, MAX_D); return -2;
-    }
+    const int rc = dispatch_dim(m->D, [&](auto dd) {
+        hipLaunchKernelGGL(gather_points_kernel<dd()>, grid, block, 0, s, m->d_desc, m->d_gchunk, P, m->d_pidx_off, m->d_pidx,
+                           d_X, d_y, xs, ys);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }

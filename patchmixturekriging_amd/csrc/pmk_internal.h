@@ -218,22 +218,21 @@ namespace pmk {
 
 // ---- launchers implemented in the .hip files (all enqueue on `s`) ----
 // precision-generic kernels live in namespaces f64 / f32 (the same sources compiled twice)
+// launch_kernel_matrix_slabs, launch_items, launch_items_multi: th non-null is that descriptor for every patch, null the
+// model's per-patch device arrays (pmk_dispatch.h)
 #define PMK_DECLARE_REAL_LAUNCHERS(NS)                                                                              \
     namespace NS {                                                                                                   \
-    int launch_kernel_matrix_slabs(const pmk_model *m, const pmk_kernel_desc &th, double sigma2, hipStream_t s,      \
+    int launch_kernel_matrix_slabs(const pmk_model *m, const pmk_kernel_desc *th, double sigma2, hipStream_t s,      \
                                    int64_t p0, int64_t np, bool diag_only);                                          \
     int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np);                                        \
     int launch_backsolve(pmk_model *m, hipStream_t s, int64_t p0, int64_t np);                                       \
     int launch_ninv_from_slabs(pmk_model *m, hipStream_t s);                                                         \
     int set_device_attributes();                                                                                     \
     int build_strip_tasks(pmk_query *q, hipStream_t s);                                                              \
-    int launch_items(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                        \
+    int launch_items(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                        \
     int launch_solve_multi(pmk_model *m, hipStream_t s);                                                             \
-    int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s);                                  \
+    int launch_items_multi(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
     int launch_loo(pmk_model *m, hipStream_t s);                                                                     \
-    int launch_kernel_matrix_slabs_patches(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np);               \
-    int launch_items_patches(pmk_query *q, hipStream_t s);                                                           \
-    int launch_items_multi_patches(pmk_query *q, hipStream_t s);                                                     \
     int launch_evidence(const pmk_model *m, int R, double *d_logdet, double *d_quad, hipStream_t s);                 \
     int launch_loo_values(const pmk_model *m, int R, double *d_res, double *d_var, hipStream_t s);                   \
     int launch_gather_points(const pmk_model *m, const double *d_X, const double *d_y, hipStream_t s);               \

@@ -1,17 +1,9 @@
 // K1 (kernel-matrix build), K5 (query-side BSP search + item list), K6 (mixture) and small helpers.
 
 #include "pmk_device.h"
+#include "pmk_dispatch.h"
 
 namespace pmk {
-
-#define PMK_DISPATCH_D(D, CALL)                                    \
-    switch (D) {                                                   \
-    case 1: { constexpr int DD = 1; CALL; } break;                 \
-    case 2: { constexpr int DD = 2; CALL; } break;                 \
-    case 3: { constexpr int DD = 3; CALL; } break;                 \
-    case 4: { constexpr int DD = 4; CALL; } break;                 \
-    default: set_error("unsupported input dimension %d (1..%d)", (int)(D), MAX_D); return -2; \
-    }
 
 // Dense n x m kernel matrix for the host API (constructkernelmatrix, RKHS.jl:4-34 and :95-110).
 // symmetric: entry (i,j) is evaluated as k(x_max, x_min) -- the lower-triangle value of the
@@ -43,8 +35,12 @@ int launch_kernel_matrix_dense(const pmk_kernel_desc &th, int D, int64_t n, cons
                                bool symmetric, hipStream_t s)
 {
     dim3 grid((unsigned)((n + 63) / 64), (unsigned)((mcols + 63) / 64));
-    PMK_DISPATCH_D(D, hipLaunchKernelGGL(kmat_dense_kernel<DD>, grid, dim3(256), 0, s, th, n, d_xs, ldx, mcols, d_zs,
-                                         ldz, d_K, ldk, symmetric ? 1 : 0));
+    const int rc = dispatch_dim(D, [&](auto dd) {
+        hipLaunchKernelGGL(kmat_dense_kernel<dd()>, grid, dim3(256), 0, s, th, n, d_xs, ldx, mcols, d_zs, ldz, d_K, ldk,
+                           symmetric ? 1 : 0);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }
@@ -77,13 +73,16 @@ int launch_query_mean(const pmk_kernel_desc *th, int nth, int D, int64_t n, cons
                       int64_t nq, const double *d_xq, double *d_yq, hipStream_t s)
 {
     dim3 grid((unsigned)((nq + 63) / 64));
-    if (nth == 1) {
-        PMK_DISPATCH_D(D, hipLaunchKernelGGL((query_mean_kernel<DD, false>), grid, dim3(64), 0, s, *th, nullptr, n, d_xs, ldx,
-                                             d_c, nq, d_xq, d_yq));
-    } else {
-        PMK_DISPATCH_D(D, hipLaunchKernelGGL((query_mean_kernel<DD, true>), grid, dim3(64), 0, s, pmk_kernel_desc{}, th, n, d_xs,
-                                             ldx, d_c, nq, d_xq, d_yq));
-    }
+    const int rc = dispatch_dim(D, [&](auto dd) {
+        if (nth == 1)
+            hipLaunchKernelGGL((query_mean_kernel<dd(), false>), grid, dim3(64), 0, s, *th, nullptr, n, d_xs, ldx, d_c, nq, d_xq,
+                               d_yq);
+        else
+            hipLaunchKernelGGL((query_mean_kernel<dd(), true>), grid, dim3(64), 0, s, pmk_kernel_desc{}, th, n, d_xs, ldx, d_c,
+                               nq, d_xq, d_yq);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }
@@ -341,9 +340,7 @@ int set_plan_attributes()
 
 static int launch_plan(pmk_query *q, double radius, double delta, bool fill, hipStream_t s)
 {
-    int rc = 0;
-    PMK_DISPATCH_D(q->m->D, rc = launch_plan_D<DD>(q, radius, delta, fill, s));
-    return rc;
+    return dispatch_dim(q->m->D, [&](auto dd) { return launch_plan_D<dd()>(q, radius, delta, fill, s); });
 }
 
 int launch_plan_count(pmk_query *q, double radius, double delta, hipStream_t s) { return launch_plan(q, radius, delta, false, s); }
@@ -644,13 +641,12 @@ int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out
 {
     if (n == 0) return 0;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    switch (q->m->D) {
-    case 1: hipLaunchKernelGGL(export_requests_kernel<1>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query, q->d_item_region, q->d_xq, x_out, region_out); break;
-    case 2: hipLaunchKernelGGL(export_requests_kernel<2>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query, q->d_item_region, q->d_xq, x_out, region_out); break;
-    case 3: hipLaunchKernelGGL(export_requests_kernel<3>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query, q->d_item_region, q->d_xq, x_out, region_out); break;
-    case 4: hipLaunchKernelGGL(export_requests_kernel<4>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query, q->d_item_region, q->d_xq, x_out, region_out); break;
-    default: set_error("input dimension %d not supported", q->m->D); return -2;
-    }
+    const int rc = dispatch_dim(q->m->D, [&](auto dd) {
+        hipLaunchKernelGGL(export_requests_kernel<dd()>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query,
+                           q->d_item_region, q->d_xq, x_out, region_out);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }

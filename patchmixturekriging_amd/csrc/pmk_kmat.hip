@@ -1,4 +1,5 @@
 // K1: batched kernel-matrix build into the factorisation slabs (compiled for real = double and float).
+#include "pmk_dispatch.h"
 #include "pmk_real.h"
 
 namespace pmk {
@@ -87,57 +88,24 @@ __global__ __launch_bounds__(256) void kmat_slab_kernel(const PatchDesc *__restr
     }
 }
 
-template <int D>
-static int launch_slab_D(const pmk_model *m, const pmk_kernel_desc &th, double sigma2, hipStream_t s, int64_t p0, int64_t np,
-                         bool diag_only)
+// th non-null: this theta and sigma2 for every patch.  th null (per-patch hyperparameters): the model's device arrays from
+// patch p0 on, and always the whole lower triangle -- the fused build evaluates tiles inside the factorisation's step
+// launches, which know one theta.
+int launch_kernel_matrix_slabs(const pmk_model *m, const pmk_kernel_desc *th, double sigma2, hipStream_t s, int64_t p0,
+                               int64_t np, bool diag_only)
 {
+    if (!th) diag_only = false;
     const int nt64 = m->max_nt * (TILE / 64);
-    dim3 grid((unsigned)(diag_only ? 3 * m->max_nt : nt64 * (nt64 + 1) / 2), (unsigned)np);
-    if (th.family == PMK_SPLINE34)
-        hipLaunchKernelGGL((kmat_slab_kernel<D, PMK_SPLINE34>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, th, sigma2, diag_only, (const real *)m->d_diag);
-    else
-        hipLaunchKernelGGL((kmat_slab_kernel<D, 0>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, th, sigma2, diag_only, (const real *)m->d_diag);
+    const dim3 grid((unsigned)(diag_only ? 3 * m->max_nt : nt64 * (nt64 + 1) / 2), (unsigned)np);
+    const int rc = dispatch_hyper(m, th, [&](auto dd, auto fam, auto pp) {
+        hipLaunchKernelGGL((kmat_slab_kernel<dd(), fam(), pp()>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x,
+                           (real *)m->d_a, hyper_th<pp()>(m, th, p0), hyper_sigma2<pp()>(m, sigma2, p0), diag_only,
+                           (const real *)m->d_diag);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
-}
-
-// per-patch hyperparameters: always the whole lower triangle (the fused build evaluates tiles inside the factorisation's
-// step launches, which know one theta).  FAM = PMK_SPLINE34 if every patch is Spline34, else the run-time family switch.
-template <int D>
-static int launch_slab_patches_D(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
-{
-    const int nt64 = m->max_nt * (TILE / 64);
-    dim3 grid((unsigned)(nt64 * (nt64 + 1) / 2), (unsigned)np);
-    if (m->hyper_s34)
-        hipLaunchKernelGGL((kmat_slab_kernel<D, PMK_SPLINE34, true>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, (const pmk_kernel_desc *)(m->d_ths + p0), (const double *)(m->d_sigma2s + p0), false, (const real *)m->d_diag);
-    else
-        hipLaunchKernelGGL((kmat_slab_kernel<D, 0, true>), grid, dim3(256), 0, s, m->d_desc + p0, (const real *)m->d_x, (real *)m->d_a, (const pmk_kernel_desc *)(m->d_ths + p0), (const double *)(m->d_sigma2s + p0), false, (const real *)m->d_diag);
-    PMK_HIP(hipGetLastError());
-    return 0;
-}
-
-#define PMK_DISPATCH_D(D, CALL)                                    \
-    switch (D) {                                                   \
-    case 1: { constexpr int DD = 1; CALL; } break;                 \
-    case 2: { constexpr int DD = 2; CALL; } break;                 \
-    case 3: { constexpr int DD = 3; CALL; } break;                 \
-    case 4: { constexpr int DD = 4; CALL; } break;                 \
-    default: set_error("unsupported input dimension %d (1..%d)", (int)(D), MAX_D); return -2; \
-    }
-
-int launch_kernel_matrix_slabs(const pmk_model *m, const pmk_kernel_desc &th, double sigma2, hipStream_t s,
-                               int64_t p0, int64_t np, bool diag_only)
-{
-    int rc = 0;
-    PMK_DISPATCH_D(m->D, rc = launch_slab_D<DD>(m, th, sigma2, s, p0, np, diag_only));
-    return rc;
-}
-
-int launch_kernel_matrix_slabs_patches(const pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
-{
-    int rc = 0;
-    PMK_DISPATCH_D(m->D, rc = launch_slab_patches_D<DD>(m, s, p0, np));
-    return rc;
 }
 
 }  // namespace PMK_NS

@@ -15,6 +15,7 @@
 // HBM traffic of the solve: the lower triangle of L twice (forward row-wise, backward column-wise) for all R columns at
 // once, plus 2 x ld x 16 elements of Y / C per patch.  The items kernel reads only the points and C_r (L2-resident per
 // region); it is VALU bound on the kernel evaluations.
+#include "pmk_dispatch.h"
 #include "pmk_mfma.h"
 
 namespace pmk {
@@ -243,57 +244,19 @@ __global__ __launch_bounds__(IM_THREADS) void item_means_kernel(const PatchDesc 
         }
 }
 
-int launch_items_multi(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s)
+// th null: the model's per-patch kernels (the convention of pmk_dispatch.h)
+int launch_items_multi(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
 {
     pmk_model *m = q->m;
     if (q->mchunks == 0) return 0;
     const unsigned grid = (unsigned)((q->mchunks + IM_THREADS / 64 - 1) / (IM_THREADS / 64));
-    const bool s34 = th.family == PMK_SPLINE34;
-    switch (m->D) {
-#define PMK_CASE(DD)                                                                                                     \
-    case DD:                                                                                                             \
-        if (s34)                                                                                                         \
-            hipLaunchKernelGGL((item_means_kernel<DD, PMK_SPLINE34>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,     \
-                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->um_ld, q->d_um);              \
-        else                                                                                                             \
-            hipLaunchKernelGGL((item_means_kernel<DD, 0>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,                \
-                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, th, q->um_ld, q->d_um);              \
-        break;
-        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
-#undef PMK_CASE
-    default:
-        set_error("prediction supports input dimension 1..4, got %d", m->D);
-        return -2;
-    }
-    PMK_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_items_multi_patches(pmk_query *q, hipStream_t s)
-{
-    pmk_model *m = q->m;
-    if (q->mchunks == 0) return 0;
-    const unsigned grid = (unsigned)((q->mchunks + IM_THREADS / 64 - 1) / (IM_THREADS / 64));
-    switch (m->D) {
-#define PMK_CASE(DD)                                                                                                     \
-    case DD:                                                                                                             \
-        if (m->hyper_s34)                                                                                                \
-            hipLaunchKernelGGL((item_means_kernel<DD, PMK_SPLINE34, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc, \
-                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->um_ld, q->d_um); \
-        else                                                                                                             \
-            hipLaunchKernelGGL((item_means_kernel<DD, 0, true>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,          \
-                               (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks, \
-                               q->d_sorted_item, q->d_item_query, q->d_xq, (const pmk_kernel_desc *)m->d_ths, q->um_ld, q->d_um); \
-        break;
-        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
-#undef PMK_CASE
-    default:
-        set_error("prediction supports input dimension 1..4, got %d", m->D);
-        return -2;
-    }
+    const int rc = dispatch_hyper(m, th, [&](auto dd, auto fam, auto pp) {
+        hipLaunchKernelGGL((item_means_kernel<dd(), fam(), pp()>), dim3(grid), dim3(IM_THREADS), 0, s, m->d_desc,
+                           (const real *)m->d_x, (const real *)m->d_cm, q->d_roff, q->d_mcpre, (int)m->P, q->mchunks,
+                           q->d_sorted_item, q->d_item_query, q->d_xq, hyper_th<pp()>(m, th), q->um_ld, q->d_um);
+        return 0;
+    });
+    if (rc) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }

@@ -15,19 +15,16 @@ static int no_gpu(const char *what)
 
 #define PMK_STUB_REAL(NS)                                                                                          \
     namespace NS {                                                                                                  \
-    int launch_kernel_matrix_slabs(const pmk_model *, const pmk_kernel_desc &, double, hipStream_t, int64_t, int64_t, bool) { return no_gpu("launch_kernel_matrix_slabs"); } \
+    int launch_kernel_matrix_slabs(const pmk_model *, const pmk_kernel_desc *, double, hipStream_t, int64_t, int64_t, bool) { return no_gpu("launch_kernel_matrix_slabs"); } \
     int launch_cholesky(pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_cholesky"); }         \
     int launch_backsolve(pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_backsolve"); }       \
     int launch_ninv_from_slabs(pmk_model *, hipStream_t) { return no_gpu("launch_ninv_from_slabs"); }             \
     int set_device_attributes() { return 0; }                                                                       \
     int build_strip_tasks(pmk_query *, hipStream_t) { return no_gpu("build_strip_tasks"); }                        \
-    int launch_items(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_items"); }         \
+    int launch_items(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items"); }         \
     int launch_solve_multi(pmk_model *, hipStream_t) { return no_gpu("launch_solve_multi"); }                       \
-    int launch_items_multi(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_items_multi"); } \
+    int launch_items_multi(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_multi"); } \
     int launch_loo(pmk_model *, hipStream_t) { return no_gpu("launch_loo"); }                                       \
-    int launch_kernel_matrix_slabs_patches(const pmk_model *, hipStream_t, int64_t, int64_t) { return no_gpu("launch_kernel_matrix_slabs_patches"); } \
-    int launch_items_patches(pmk_query *, hipStream_t) { return no_gpu("launch_items_patches"); }                   \
-    int launch_items_multi_patches(pmk_query *, hipStream_t) { return no_gpu("launch_items_multi_patches"); }       \
     int launch_evidence(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_evidence"); } \
     int launch_loo_values(const pmk_model *, int, double *, double *, hipStream_t) { return no_gpu("launch_loo_values"); } \
     int launch_gather_points(const pmk_model *, const double *, const double *, hipStream_t) { return no_gpu("launch_gather_points"); } \

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <tuple>
 
+#include "pmk_dispatch.h"
 #include "pmk_mfma.h"
 
 namespace pmk {
@@ -338,9 +339,32 @@ __global__ __launch_bounds__(PRED_THREADS, 2) void predict_strip_kernel(const Pa
     }
 }
 
-// The per-patch instantiations are compiled in a translation unit of their own (pmk_predict_patches.hip includes this
-// file with PMK_PREDICT_PATCHES_TU defined): the strip kernel is the longest compile of the library, and the two halves
-// then build side by side.  This unit holds the uniform launcher and the strip tasks, that one launch_items_patches.
+// The strip kernel is the longest compile of the library, so its instantiations are split over two translation units
+// that build side by side: this file emits launch_strips<false> (one theta by value), and pmk_predict_patches.hip, which
+// includes this file with PMK_PREDICT_PATCHES_TU defined, emits launch_strips<true> (theta from the model's device
+// array) and nothing else.  launch_items below picks between the two.
+template <bool PP>
+int launch_strips(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
+{
+    pmk_model *m = q->m;
+    const int64_t stride = (int64_t)m->max_nt * TILE * TQ;
+    const StripTask *d_tasks = reinterpret_cast<const StripTask *>(q->d_tasks);
+    return dispatch_dim_family(m->D, hyper_spline34(m, th), [&](auto dd, auto fam) {
+        hipLaunchKernelGGL((predict_strip_kernel<dd(), fam(), PP>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s,
+                           m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks,
+                           (int)q->ntasks, q->d_sorted_item, q->d_item_query, q->d_xq, (real *)m->d_strip, stride,
+                           hyper_th<PP>(m, th), q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk,
+                           q->d_qdiag);
+        return 0;
+    });
+}
+#ifdef PMK_PREDICT_PATCHES_TU
+template int launch_strips<true>(pmk_query *, const pmk_kernel_desc *, hipStream_t);
+#else
+template int launch_strips<false>(pmk_query *, const pmk_kernel_desc *, hipStream_t);
+extern template int launch_strips<true>(pmk_query *, const pmk_kernel_desc *, hipStream_t);
+#endif
+
 #ifndef PMK_PREDICT_PATCHES_TU
 #if defined(PMK_TRACE) && !defined(PMK_REAL_F32)
 extern "C" int pmk_trace_sync_stats(unsigned long long *out, int reset)
@@ -433,65 +457,12 @@ int build_strip_tasks(pmk_query *q, hipStream_t s)
     return 0;
 }
 
-int launch_items(pmk_query *q, const pmk_kernel_desc &th, hipStream_t s)
+// th null: the model's per-patch kernels (the convention of pmk_dispatch.h)
+int launch_items(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
 {
-    pmk_model *m = q->m;
     if (q->ntasks == 0) return 0;
-    const int64_t stride = (int64_t)m->max_nt * TILE * TQ;
-    const StripTask *d_tasks = reinterpret_cast<const StripTask *>(q->d_tasks);
     if (q->nsync > 0) PMK_HIP(hipMemsetAsync(q->d_sync, 0, sizeof(uint32_t) * (size_t)q->nsync, s));
-    const bool s34 = th.family == PMK_SPLINE34;
-    switch (m->D) {
-#define PMK_CASE(DD)                                                                                                   \
-    case DD:                                                                                                           \
-        if (s34)                                                                                                       \
-            hipLaunchKernelGGL((predict_strip_kernel<DD, PMK_SPLINE34>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s, \
-                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
-                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, th, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
-        else                                                                                                           \
-            hipLaunchKernelGGL((predict_strip_kernel<DD, 0>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s,  \
-                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
-                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, th, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
-        break;
-        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
-#undef PMK_CASE
-    default:
-        set_error("prediction supports input dimension 1..4, got %d", m->D);
-        return -2;
-    }
-    PMK_HIP(hipGetLastError());
-    return 0;
-}
-
-#else  // PMK_PREDICT_PATCHES_TU
-
-// the per-patch strips of pmk_query_items_fitted: theta from the model's device array.  FAM = PMK_SPLINE34 if every patch
-// is Spline34, else the run-time family switch
-int launch_items_patches(pmk_query *q, hipStream_t s)
-{
-    pmk_model *m = q->m;
-    if (q->ntasks == 0) return 0;
-    const int64_t stride = (int64_t)m->max_nt * TILE * TQ;
-    const StripTask *d_tasks = reinterpret_cast<const StripTask *>(q->d_tasks);
-    if (q->nsync > 0) PMK_HIP(hipMemsetAsync(q->d_sync, 0, sizeof(uint32_t) * (size_t)q->nsync, s));
-    switch (m->D) {
-#define PMK_CASE(DD)                                                                                                   \
-    case DD:                                                                                                           \
-        if (m->hyper_s34)                                                                                              \
-            hipLaunchKernelGGL((predict_strip_kernel<DD, PMK_SPLINE34, true>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s, \
-                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
-                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, (const pmk_kernel_desc *)m->d_ths, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
-        else                                                                                                           \
-            hipLaunchKernelGGL((predict_strip_kernel<DD, 0, true>), dim3((unsigned)q->strip_grid), dim3(PRED_THREADS), 0, s,  \
-                               m->d_desc, (real *)m->d_x, (real *)m->d_a, (real *)m->d_inv, (real *)m->d_c, d_tasks, (int)q->ntasks, q->d_sorted_item,  \
-                               q->d_item_query, q->d_xq, (real *)m->d_strip, stride, (const pmk_kernel_desc *)m->d_ths, q->d_sync, (int)q->round_base, q->min_v, q->d_u, q->d_v, m->ctx->d_clk, q->d_qdiag);  \
-        break;
-        PMK_CASE(1) PMK_CASE(2) PMK_CASE(3) PMK_CASE(4)
-#undef PMK_CASE
-    default:
-        set_error("prediction supports input dimension 1..4, got %d", m->D);
-        return -2;
-    }
+    if (int rc = th ? launch_strips<false>(q, th, s) : launch_strips<true>(q, nullptr, s)) return rc;
     PMK_HIP(hipGetLastError());
     return 0;
 }
