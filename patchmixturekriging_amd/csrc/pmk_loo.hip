@@ -161,7 +161,7 @@ __global__ __launch_bounds__(STRIP_THREADS, 2) void loo_strip_kernel(const Patch
     }
 }
 
-// strip tasks of the model (they depend on the patch sizes only) and their queues
+// strip tasks of the model (they depend on the patch sizes only) and their queues.  Mirrored by tasks() in tests/_loo_schedule.py.
 static int build_loo_tasks(pmk_model *m, hipStream_t s)
 {
     std::vector<LooTask> all;

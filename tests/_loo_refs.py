@@ -1,5 +1,5 @@
 """Long-double references for the model-selection scores (tests/test_model_selection_abi.py,
-tests/test_gpu_model_selection.py): leave-one-out residuals and variances in closed form (Rasmussen & Williams, Gaussian
+tests/test_gpu_model_selection.py, tests/test_gpu_loo_schedule.py): leave-one-out residuals and variances in closed form (Rasmussen & Williams, Gaussian
 Processes for Machine Learning, eq. 5.10-5.12) and the two terms of the log marginal likelihood (eq. 5.8).
 
 numpy.longdouble (x87 extended, 64-bit mantissa), a plain column Cholesky and plain row substitutions -- nothing blocked,
@@ -62,7 +62,24 @@ def loo_reference(K, sigma2, Y):
     return out
 
 
+def trtri_colnorms(L):
+    """squared column norms of L^-1 in double by LAPACK dtrtri, where long double would take too long"""
+    import scipy.linalg as sla
+    Li, info = sla.lapack.dtrtri(np.asfortranarray(L), lower=1)
+    assert info == 0
+    return (Li * Li).sum(0)
+
+
 def sum_ld(terms):
     """(sum, sum of magnitudes) of the terms in long double"""
     t = np.asarray(terms, dtype=LD)
     return t.sum(), np.abs(t).sum()
+
+
+def summation_error_and_bound(n, got, terms):
+    """|got - sum terms| <= 2 (n + 4) 2^-53 sum |terms|: worst-case recursive summation plus two roundoffs per term (the
+    device accumulates in double in both precisions)"""
+    s, mag = sum_ld(terms)
+    bound = 2 * (n + 4) * U64 * float(mag)
+    err = abs(float(LD(got) - s))
+    return err, bound

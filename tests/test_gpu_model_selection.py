@@ -16,7 +16,6 @@ import os
 
 import numpy as np
 import pytest
-import scipy.linalg as sla
 
 import patchmixturekriging_amd as pmk
 from patchmixturekriging_amd import _lib
@@ -142,13 +141,7 @@ def test_d_and_residuals_end_to_end(name, dtype, k):
 
 
 # ------------------------------------------------------------------------------------ 6. evidence
-def _summation_error_and_bound(n, got, terms):
-    """|got - sum terms| <= 2 (n + 4) 2^-53 sum |terms|: worst-case recursive summation plus two roundoffs per term (the
-    device accumulates in double in both precisions)"""
-    s, mag = LR.sum_ld(terms)
-    bound = 2 * (n + 4) * LR.U64 * float(mag)
-    err = abs(float(LD(got) - s))
-    return err, bound
+_summation_error_and_bound = LR.summation_error_and_bound
 
 
 @pytest.mark.parametrize("name, dtype, k", CASES, ids=CASE_IDS)
@@ -253,10 +246,7 @@ def test_multi_output_columns():
 
 
 # ------------------------------------------------------------------------------------ 9. shapes
-def _trtri_colnorms(L):
-    Li, info = sla.lapack.dtrtri(np.asfortranarray(L), lower=1)
-    assert info == 0
-    return (Li * Li).sum(0)
+_trtri_colnorms = LR.trtri_colnorms
 
 
 def oracle_f(X):
