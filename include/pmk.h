@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -361,6 +361,39 @@ int  pmk_model_loo(pmk_model *m);
 int  pmk_model_get_loo(pmk_model *m, double *const *res, double *const *var);
 /* R columns: RES[r] is n[r] x R column-major, leading dimension ldres[r] >= n[r]; var is shared by the columns */
 int  pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ldres, double *const *var);
+
+/* ---- blended leave-one-out: cross-validate the MIXTURE predictor, no refits ---------------------------------------------
+ * The scores above are per patch; what is deployed is the blend of querymixtureGP! (mixtureGP.jl:159-294): home leaf plus
+ * the neighbours within radius, weights phi_w(|t|), normalised.  Leaving global point j out of the model removes it from
+ * every patch that holds it and changes nothing else (the patches are independent GPs; the tree is held fixed), so for
+ * the query x_j an item (j, region r) is
+ *   member (patch r holds j as row i):  u = y_i - c_i / d_i,  v = 1 / d_i if noisy, else max(1 / d_i - sigma2_r, min_v):
+ *     the Schur complement of row i of U = K + sigma2 I, from d = diag(U^-1) of pmk_model_loo.  Double, IEEE division: the
+ *     values numpy computes from pmk_model_get_loo's res and var.  sigma2_r is the noise the resident factor was fitted
+ *     with (pmk_model_fit's, or pmk_model_fit_patches' of that patch).  A patch with info != 0 gives NaN in both.
+ *   non-member (a neighbour region reached with radius > eps, which never saw j):  the (u, v) of pmk_query_items_fitted for
+ *     that (point, region), the same bits, pmk_query_set_diag's addend honoured; with noisy, sigma2_r is added with one
+ *     add after the clamp.  NaN in both if the patch's factorisation failed.
+ * and blending these items with pmk_query_mix is exactly the leave-one-out of the blended predictor.  In 1 / d - sigma2
+ * the two terms agree to within the patch's leverage at the point: where the data determine the point (1 / d close to
+ * sigma2) the latent variance loses about log2(sigma2 / (1 / d - sigma2)) bits, and is clamped at min_v like any
+ * predictive variance; the noisy form has no subtraction.
+ * Limits.  The scores use the RESIDENT y and c: after pmk_model_set_weights they mean what the caller makes of them.  Only
+ * the single-output path: multi-output targets and the trend are not covered.  Not available through the sharded /
+ * all-gather exchanges.  Stage timer "loo_items" (and "items" inside it, if and only if strips ran). */
+/* stage 2 for a query whose points ARE the model's training points: query j is global point j of
+ * pmk_model_create_from_bsp (Nq == N).  After pmk_query_plan, instead of pmk_query_items*; pmk_query_mix, pmk_query_fetch(_dev)
+ * and pmk_query_debug then work unchanged.  n_member / n_strip (either may be NULL): how many items took each route; with
+ * n_strip == 0 no strip kernel is launched and no inner query is created.  Blocks once for the number of non-members and,
+ * if there are any, once more while the inner query of explicit items is set up (as pmk_query_create_items does); the
+ * strips, the scatter and everything after only enqueue.
+ * Refusals, before any launch: -1 not planned or not fitted; -3 the model was not made by pmk_model_create_from_bsp,
+ * Nq != N, the model does not hold every leaf, it holds no kernels, or pmk_model_loo has not run since the last fit. */
+int  pmk_query_items_loo(pmk_query *q, int noisy, int64_t *n_member, int64_t *n_strip);
+/* one-shot: create(X) + plan + items_loo + mix + fetch, like pmk_predict_mixture_fitted; X: the N training points in
+ * global order (host or device pointer) */
+int  pmk_predict_mixture_loo(pmk_model *m, const pmk_kernel_desc *weight_th, const double *X,
+                             double radius, double delta, int noisy, double *Yq, double *Vq);
 
 /* ---- per-patch kernels and noise ---------------------------------------------------------------------------------------
  * MixtureGPType carries one noise variance per patch (sigma2_set::Vector, mixtureGP.jl:44,114), and fitmixtureGP!

@@ -21,7 +21,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
-       selectmixtureGP!, selectcandidates
+       selectmixtureGP!, selectcandidates, loomixtureGP_blend
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -686,6 +686,40 @@ function loomixtureGPmulti(η::MixtureGPType{T}, R::Integer) where T
                                      (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
                                      η.model, [pointer(A) for A in RES], ldres, [pointer(a) for a in var]), "pmk_model_get_loo_multi")
     return [A[:, 1:R] for A in RES], var
+end
+
+"""loomixtureGP_blend(η, root, radius, δ, weight_θ, X; noisy = false, counts = false) -> (μ, v): the leave-one-out of the
+BLENDED predictor at every training point, without refitting: what querymixtureGP! would predict at column j of X had η
+been fitted without point j, the tree held fixed.  η: built by MixtureGPType(root, X, ε) and fitted; X: the same D x N
+matrix.  An item whose patch holds the point comes from the resident leave-one-out values (pmk_model_loo, run here), any
+other item from the strips (pmk_query_items_loo).  noisy: variances of the observation (each patch's σ² included) rather
+than of the latent field.  counts = true runs the staged calls and returns (μ, v, n_member, n_strip)."""
+function loomixtureGP_blend(η::MixtureGPType{Float64}, root, radius::Float64, δ::Float64, weight_θ, X::Matrix{Float64};
+                            noisy::Bool = false, counts::Bool = false)
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before loomixtureGP_blend"))
+    η.N_global > 0 || throw(ArgumentError("this η was built from lists of patches: build it with MixtureGPType(root, X, ε)"))
+    N = size(X, 2)
+    N == η.N_global || throw(ArgumentError("X has $N points, the model $(η.N_global)"))
+    μ = Vector{Float64}(undef, N); v = Vector{Float64}(undef, N)
+    check(ccall((:pmk_model_loo, libpmk), Cint, (Ptr{Cvoid},), η.model), "pmk_model_loo")
+    if !counts
+        check(ccall((:pmk_predict_mixture_loo, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Ptr{Float64}, Float64, Float64, Cint, Ptr{Float64}, Ptr{Float64}),
+                    η.model, Ref(desc(weight_θ)), X, radius, δ, noisy ? 1 : 0, μ, v), "pmk_predict_mixture_loo")
+        return μ, v
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL); nm = Ref{Int64}(0); ns = Ref{Int64}(0)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, N, X, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_items_loo, libpmk), Cint, (Ptr{Cvoid}, Cint, Ref{Int64}, Ref{Int64}), q[], noisy ? 1 : 0, nm, ns),
+              "pmk_query_items_loo")
+        check(ccall((:pmk_query_mix, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, N), "pmk_query_mix")
+        check(ccall((:pmk_query_fetch, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), q[], μ, v), "pmk_query_fetch")
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+    return μ, v, nm[], ns[]
 end
 
 # ------------------------------------------------------------------------------------------ kriging with a trend

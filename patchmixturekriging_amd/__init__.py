@@ -18,7 +18,7 @@ from .mixture import (DeviceModel, DeviceQuery, MixtureGPDebugType, MixtureGPTyp
                       logevidencemixtureGP_multi, loomixtureGP, loomixtureGP_multi, queryinner, querymixtureGP,
                       querymixtureGP_, querymixtureGP_multi, fitmixtureGP_patches_, querymixtureGP_patches,
                       querymixtureGP_multi_patches, select_candidates, selectmixtureGP_, fitmixtureGP_trend_,
-                      TrendRankException)
+                      TrendRankException, loomixtureGP_blend, selectblendGP_)
 from .partition import (BinaryNode, HyperplaneType, PartitionDataType, array2matrix,  # noqa: F401
                         convert2itpindex, fetchhyperplanes, findneighbourpartitions, findpartition,
                         getpartitionlines_,

@@ -1253,6 +1253,8 @@ void pmk_query_destroy(pmk_query *q)
     if (q->d_tasks) (void)hipFree(q->d_tasks);
     if (q->d_sync) (void)hipFree(q->d_sync);
     dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre);
+    dev_free(q->d_loo_x);               // base of the leave-one-out arena (loo_reserve)
+    pmk_query_destroy(q->loo_inner);
     delete q;
 }
 
@@ -1637,6 +1639,121 @@ int pmk_predict_mixture_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, i
     if (rc) return rc;
     if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_fitted(q)) &&
         !(rc = pmk_query_mix(q, weight_th, 0, Nq)))
+        rc = pmk_query_fetch(q, Yq, Vq);
+    pmk_query_destroy(q);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------ blended leave-one-out
+// buffers of pmk_query_items_loo for up to `total` sorted items, grow only.  ONE allocation; d_loo_x is its base.
+static int loo_reserve(pmk_query *q, int64_t total)
+{
+    if (total <= q->loo_cap) return 0;
+    dev_free(q->d_loo_x);
+    q->d_loo_diag = nullptr; q->d_loo_ru = nullptr; q->d_loo_rv = nullptr; q->d_loo_off = nullptr;
+    q->d_loo_mark = nullptr; q->d_loo_region = nullptr;
+    q->loo_cap = 0;
+    const size_t cap = (size_t)(total + total / 8 + 1024);
+    ArenaLayout a;
+    const size_t o_x = a.add(sizeof(double) * cap * (size_t)q->m->D), o_d = a.add(sizeof(double) * cap),
+                 o_u = a.add(sizeof(double) * cap), o_v = a.add(sizeof(double) * cap), o_o = a.add(sizeof(int64_t) * (cap + 1)),
+                 o_m = a.add(sizeof(int32_t) * (cap + 1)), o_r = a.add(sizeof(int32_t) * cap);
+    char *base = nullptr;
+    PMK_HIP(hipMalloc((void **)&base, a.bytes));
+    q->d_loo_x = reinterpret_cast<double *>(base + o_x);               // o_x == 0
+    q->d_loo_diag = reinterpret_cast<double *>(base + o_d);
+    q->d_loo_ru = reinterpret_cast<double *>(base + o_u);
+    q->d_loo_rv = reinterpret_cast<double *>(base + o_v);
+    q->d_loo_off = reinterpret_cast<int64_t *>(base + o_o);
+    q->d_loo_mark = reinterpret_cast<int32_t *>(base + o_m);
+    q->d_loo_region = reinterpret_cast<int32_t *>(base + o_r);
+    q->loo_cap = (int64_t)cap;
+    return 0;
+}
+
+// every refusal of the blended leave-one-out that depends on the model, host state only: nothing is launched before this
+// returns 0.  Nq: the number of query points that will stand for the training points.
+static int loo_model_ok(const pmk_model *m, int64_t Nq, const char *who)
+{
+    if (!m->fitted) { set_error("%s: model is not fitted", who); return -1; }
+    if (!m->from_bsp) {
+        set_error("%s: the model was not made by pmk_model_create_from_bsp (no map from patch rows to global points)", who);
+        return -3;
+    }
+    if (Nq != m->N_global) {
+        set_error("%s: the query has %lld points, the model %lld: query j must be global training point j", who,
+                  (long long)Nq, (long long)m->N_global);
+        return -3;
+    }
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("%s: the model holds %lld of %lld leaves; the blended leave-one-out needs every leaf", who, (long long)m->P,
+                  (long long)m->P_global);
+        return -3;
+    }
+    if (m->ths.empty()) { set_error("%s: the model holds no kernels (pmk_model_set_kernels)", who); return -3; }
+    if (!m->loo_valid) { set_error("%s: pmk_model_loo has not run on the resident factor", who); return -3; }
+    return 0;
+}
+
+int pmk_query_items_loo(pmk_query *q, int noisy, int64_t *n_member, int64_t *n_strip)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_loo: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (int rc = loo_model_ok(m, q->Nq, "pmk_query_items_loo")) return rc;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    int64_t ns = 0;
+    noisy = noisy != 0;
+    c->tic("loo_items");
+    if (q->total > 0) {
+        if ((rc = loo_reserve(q, q->total))) return rc;
+        // members: a lookup per item, and the marks of the rest
+        if ((rc = PMK_BY_DTYPE(m, launch_loo_member(q, noisy, q->d_loo_mark, s)))) return rc;
+        if (exclusive_scan_i32_to_i64(q->d_loo_mark, q->d_loo_off, q->total, &q->d_tmp, &q->tmp_bytes, s)) {
+            set_error("pmk_query_items_loo: prefix scan failed");
+            return -100;
+        }
+        PMK_HIP(hipMemcpyAsync(&ns, q->d_loo_off + q->total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        PMK_HIP(hipStreamSynchronize(s));
+    }
+    if (ns > 0) {
+        // non-members: queryinner! on the strip kernel, as explicit items of an inner query (the request / response
+        // pattern of pmk_query_predict_sharded with this process as its own leaf owner)
+        if (!q->loo_inner && (rc = pmk_query_create(m, 0, nullptr, &q->loo_inner))) return rc;
+        pmk_query *in = q->loo_inner;
+        if ((rc = PMK_BY_DTYPE(m, launch_loo_compact(q, q->d_loo_mark, q->d_loo_off, q->d_loo_x, q->d_loo_region,
+                                                     q->d_loo_diag, s))))
+            return rc;
+        if ((rc = query_set_items(in, ns, q->d_loo_x, q->d_loo_region))) return rc;
+        // the addends in request order = the inner query's item order; borrowed for this launch only (the arena is q's)
+        in->d_qdiag = q->d_qdiag ? q->d_loo_diag : nullptr;
+        in->min_v = q->min_v;
+        rc = pmk_query_items_fitted(in);
+        in->d_qdiag = nullptr;
+        if (rc) return rc;
+        if ((rc = launch_export_results(in, q->d_loo_ru, q->d_loo_rv, s))) return rc;
+        if ((rc = PMK_BY_DTYPE(m, launch_loo_scatter(q, noisy, q->d_loo_mark, q->d_loo_off, q->d_loo_ru, q->d_loo_rv, s))))
+            return rc;
+    }
+    c->toc("loo_items");
+    if (n_member) *n_member = q->total - ns;
+    if (n_strip) *n_strip = ns;
+    return 0;
+}
+
+int pmk_predict_mixture_loo(pmk_model *m, const pmk_kernel_desc *weight_th, const double *X, double radius, double delta,
+                            int noisy, double *Yq, double *Vq)
+{
+    if (!m) { set_error("pmk_predict_mixture_loo: model is NULL"); return -1; }
+    int rc = loo_model_ok(m, m->N_global, "pmk_predict_mixture_loo");
+    if (rc) return rc;
+    if (!X) { set_error("pmk_predict_mixture_loo: X is NULL"); return -2; }
+    pmk_query *q = nullptr;
+    if ((rc = pmk_query_create(m, m->N_global, X, &q))) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_loo(q, noisy, nullptr, nullptr)) &&
+        !(rc = pmk_query_mix(q, weight_th, 0, q->Nq)))
         rc = pmk_query_fetch(q, Yq, Vq);
     pmk_query_destroy(q);
     return rc;

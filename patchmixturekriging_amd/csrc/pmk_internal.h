@@ -212,6 +212,14 @@ struct pmk_query {
     int64_t *d_mcpre = nullptr; int64_t mcpre_cap = 0, mchunks = 0;   // chunks of 16 items per region: prefix [P+1]
     std::vector<int64_t> mcpre;         // host copy (source of the upload)
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
+    // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
+    // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
+    // its base (grow only); the inner query of explicit items that runs the requests, created on first need
+    double *d_loo_x = nullptr; int64_t loo_cap = 0;
+    double *d_loo_diag = nullptr, *d_loo_ru = nullptr, *d_loo_rv = nullptr;
+    int64_t *d_loo_off = nullptr;
+    int32_t *d_loo_mark = nullptr, *d_loo_region = nullptr;
+    pmk_query *loo_inner = nullptr;
 };
 
 namespace pmk {
@@ -241,6 +249,11 @@ namespace pmk {
     int launch_trend_fill(const pmk_model *m, int R, int q, hipStream_t s);                                          \
     int launch_trend_gls(pmk_model *m, int R, int q, hipStream_t s);                                                 \
     int launch_trend_loo_values(const pmk_model *m, int R, int q, double *d_res, double *d_var, hipStream_t s);      \
+    int launch_loo_member(pmk_query *q, int noisy, int32_t *d_mark, hipStream_t s);                                  \
+    int launch_loo_compact(pmk_query *q, const int32_t *d_mark, const int64_t *d_off, double *x_out,                 \
+                           int32_t *region_out, double *diag_out, hipStream_t s);                                    \
+    int launch_loo_scatter(pmk_query *q, int noisy, const int32_t *d_mark, const int64_t *d_off, const double *d_ru, \
+                           const double *d_rv, hipStream_t s);                                                       \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)

@@ -33,6 +33,9 @@ static int no_gpu(const char *what)
     int launch_trend_fill(const pmk_model *, int, int, hipStream_t) { return no_gpu("launch_trend_fill"); }         \
     int launch_trend_gls(pmk_model *, int, int, hipStream_t) { return no_gpu("launch_trend_gls"); }                 \
     int launch_trend_loo_values(const pmk_model *, int, int, double *, double *, hipStream_t) { return no_gpu("launch_trend_loo_values"); } \
+    int launch_loo_member(pmk_query *, int, int32_t *, hipStream_t) { return no_gpu("launch_loo_member"); }         \
+    int launch_loo_compact(pmk_query *, const int32_t *, const int64_t *, double *, int32_t *, double *, hipStream_t) { return no_gpu("launch_loo_compact"); } \
+    int launch_loo_scatter(pmk_query *, int, const int32_t *, const int64_t *, const double *, const double *, hipStream_t) { return no_gpu("launch_loo_scatter"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)

@@ -182,6 +182,7 @@ class DeviceModel:
         self._from_tree, self._X, self._X_global = True, None, (None if xa.device else X)
         self.leaf_base = int(leaf_base)
         self.P = int(L.pmk_model_num_patches(h))
+        self._all_leaves = self.leaf_base == 0 and self.P == int(L.pmk_bsp_num_leaves(nat.h))
         self._index = None
         off, _ = self.patch_index()
         self.n = np.diff(off)
@@ -555,6 +556,26 @@ class DeviceQuery:
         if not getattr(self.model, "_has_kernels", False):
             raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
         _lib.check(self.L.pmk_query_items_fitted(self.h), "pmk_query_items_fitted")
+
+    def items_loo(self, noisy=False):
+        """pmk_query_items_loo: stage 2 of the blended leave-one-out, for a query whose points ARE the training points of a
+        tree-built model (query j = global point j) -> (n_member, n_strip).  An item whose patch holds the point comes
+        from the resident leave-one-out values (no strip); any other item is items_fitted's.  noisy: the variances include
+        each patch's sigma2.  Follow with mix() and fetch() as after items()."""
+        m = self.model
+        if not getattr(m, "_from_tree", False):
+            raise _lib.PmkError("items_loo: the model was built from lists of patches, not by from_tree")
+        if self.Nq != m.N:
+            raise _lib.PmkError("items_loo: the query has %d points, the model %d: query j must be training point j"
+                                % (self.Nq, m.N))
+        if not getattr(m, "_all_leaves", False):
+            raise _lib.PmkError("items_loo: the model holds a shard of the leaves; the blended leave-one-out needs all")
+        if not getattr(m, "_has_kernels", False):
+            raise _lib.PmkError("the model holds no kernels: fit it first")
+        m._need(loo=True)
+        nm, ns = C.c_int64(), C.c_int64()
+        _lib.check(self.L.pmk_query_items_loo(self.h, int(bool(noisy)), C.byref(nm), C.byref(ns)), "pmk_query_items_loo")
+        return nm.value, ns.value
 
     def items_multi_fitted(self, variance=True):
         """pmk_query_items_multi_fitted: items_multi with the model's own kernels"""
@@ -1153,3 +1174,73 @@ def selectmixtureGP_(eta, y_parts, candidates, score="evidence"):
     winners = select_candidates(scores)
     fitmixtureGP_patches_(eta, y_parts, [candidates[w][0] for w in winners], [candidates[w][1] for w in winners])
     return eta, winners, scores
+
+
+
+# ---- blended leave-one-out: cross-validate what is deployed, the mixture of querymixtureGP!, without refitting.  Leaving a
+# training point out removes it from every patch that holds it; in those patches its prediction is the resident
+# leave-one-out value, in a neighbour patch that never held it the ordinary queryinner!, and the blend is the unchanged one.
+def _blend_model(eta, who):
+    model = _fitted_model(eta, who)
+    if not getattr(model, "_from_tree", False):
+        raise _lib.PmkError("%s: eta must be built by MixtureGPType.from_tree (the map from patch rows to global points)" % who)
+    if not getattr(model, "_has_kernels", False) or not model._has_factor:
+        raise _lib.PmkError("%s: fit the model first" % who)
+    return model
+
+
+def _blend_query(model, X, who):
+    if X is None:
+        X = getattr(model, "_X_global", None)
+        if X is None:
+            raise _lib.PmkError("%s: the model was built from a device array and holds no host copy of X; pass X" % who)
+    q = DeviceQuery(model, X)
+    if q.Nq != model.N:
+        raise _lib.PmkError("%s: X has %d points, the model %d" % (who, q.Nq, model.N))
+    return q
+
+
+def loomixtureGP_blend(eta, root, radius, delta, weight_theta, X=None, noisy=False):
+    """leave-one-out of the BLENDED predictor -> (mu_loo, var_loo), N values each: what querymixtureGP_patches would
+    predict at training point j had the model been fitted without j, the tree held fixed.  No refit: one plan, a lookup
+    per item whose patch holds the point, strips for the others, one mix.  eta: built by MixtureGPType.from_tree on `root`
+    and fitted (the model carries the tree; `root` keeps the argument order of the query functions).  X: the N training
+    points in global order (numpy or device array); default: the host array the model was built from.  noisy: variances
+    of the observation (each patch's sigma2 included) rather than of the latent field.  Runs loo() if it is stale."""
+    model = _blend_model(eta, "loomixtureGP_blend")
+    q = _blend_query(model, X, "loomixtureGP_blend")
+    if not model._loo_done:
+        model.loo()
+    q.plan(radius, delta)
+    q.items_loo(noisy)
+    q.mix(weight_theta)
+    return q.fetch()
+
+
+def selectblendGP_(eta, root, y, candidates, X=None):
+    """score blending settings by the leave-one-out log pseudo-likelihood of the blended predictor -> (scores [G], best).
+    candidates: a list of (radius, delta, weight_theta); scores[g] = loo_log_pseudo_likelihood(y - mu_g, var_g) with the
+    noisy variances, y the N global targets the model was fitted to; best = the first argmax, a NaN never wins.  One query
+    object, re-planned per candidate; the fit is not touched."""
+    candidates = list(candidates)
+    if not candidates:
+        raise ValueError("no candidates")
+    model = _blend_model(eta, "selectblendGP_")
+    y = np.asarray(y, dtype=np.float64)
+    if y.shape != (model.N,):
+        raise ValueError("y must hold the %d global targets" % model.N)
+    q = _blend_query(model, X, "selectblendGP_")
+    if not model._loo_done:
+        model.loo()
+    scores = np.empty(len(candidates))
+    for g, (radius, delta, weight_theta) in enumerate(candidates):
+        q.plan(radius, delta)
+        q.items_loo(True)
+        q.mix(weight_theta)
+        mu, var = q.fetch()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scores[g] = loo_log_pseudo_likelihood(y - mu, var)
+    valid = np.nonzero(~np.isnan(scores))[0]
+    if len(valid) == 0:
+        raise ValueError("every candidate scored NaN")
+    return scores, int(valid[int(np.argmax(scores[valid]))])
