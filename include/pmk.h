@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -378,9 +378,9 @@ int  pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ld
  * the two terms agree to within the patch's leverage at the point: where the data determine the point (1 / d close to
  * sigma2) the latent variance loses about log2(sigma2 / (1 / d - sigma2)) bits, and is clamped at min_v like any
  * predictive variance; the noisy form has no subtraction.
- * Limits.  The scores use the RESIDENT y and c: after pmk_model_set_weights they mean what the caller makes of them.  Only
- * the single-output path: multi-output targets and the trend are not covered.  Not available through the sharded /
- * all-gather exchanges.  Stage timer "loo_items" (and "items" inside it, if and only if strips ran). */
+ * Limits.  The scores use the RESIDENT y and c: after pmk_model_set_weights they mean what the caller makes of them.  This
+ * call is the single-output path and ignores the trend; R target columns and the trend are pmk_query_items_loo_multi's
+ * below.  Not available through the sharded / all-gather exchanges.  Stage timer "loo_items" (and "items" inside it, if and only if strips ran). */
 /* stage 2 for a query whose points ARE the model's training points: query j is global point j of
  * pmk_model_create_from_bsp (Nq == N).  After pmk_query_plan, instead of pmk_query_items*; pmk_query_mix, pmk_query_fetch(_dev)
  * and pmk_query_debug then work unchanged.  n_member / n_strip (either may be NULL): how many items took each route; with
@@ -394,6 +394,36 @@ int  pmk_query_items_loo(pmk_query *q, int noisy, int64_t *n_member, int64_t *n_
  * global order (host or device pointer) */
 int  pmk_predict_mixture_loo(pmk_model *m, const pmk_kernel_desc *weight_th, const double *X,
                              double radius, double delta, int noisy, double *Yq, double *Vq);
+
+/* ---- blended leave-one-out of the multi-output path: R target columns, with or without a trend ---------------------------
+ * The same identity on what pmk_model_solve_multi left resident (the R columns Y, the weights C, with a trend C_H, L_G and
+ * beta per patch) and d of pmk_model_loo.  For the query x_j an item (j, region r) is
+ *   member (patch r holds j as row i):  Q_ii = d_i - |L_G^-1 C_H[i, :]^T|^2 (Q_ii = d_i without a trend), and for every
+ *     column c < R:  mu_c = Y[i, c] - C[i, c] / Q_ii;  v = 1 / Q_ii if noisy, else max(1 / Q_ii - sigma2_r, min_v).  C is the
+ *     resident weight block: with a trend the universal-kriging weights C_Y - C_H beta.  Double, IEEE division, Q by the
+ *     forward substitution of the per-patch values: what numpy computes from pmk_model_get_loo_multi's RES and var.
+ *   non-member:  the item of pmk_query_items_multi_fitted for that (point, region), the same bits: mu_c with h(x)^T beta_c
+ *     added, v with the trend term added after the clamp; with noisy, sigma2_r is added with one add after that.
+ * NaN in every column and in v for a patch with info != 0 or, with a trend, tinfo != 0.  In 1 / Q - sigma2 the cancellation
+ * is that of the single-output form, with the leverage of the point under the trend model; clamped at min_v.
+ * want_var = 0: means only; no strip kernel runs anywhere, v is not computed and pmk_query_fetch_multi refuses Vq.
+ * After pmk_query_plan, instead of pmk_query_items_multi*; pmk_query_mix_multi, pmk_query_fetch_multi(_dev) and
+ * pmk_query_get_items_multi then serve unchanged.  n_member / n_other (either may be NULL): how many items took each route;
+ * with n_other == 0 nothing runs after the scan of the marks and no inner query is created.  Blocks as pmk_query_items_loo.
+ * Refusals, before any launch: those of pmk_query_items_loo, and -3 if pmk_model_solve_multi has not run on the resident
+ * factor (a new fit, pmk_model_set_targets_multi* and pmk_model_set_trend each make it stale).  pmk_query_items_loo itself
+ * keeps its bits and still ignores the trend.  Limits: no sharded or all-gather exchange; the model must hold every leaf.
+ * Stage timer "loo_items_multi" ("items_multi" and "trend_items" inside it, if and only if there are non-members). */
+int  pmk_query_items_loo_multi(pmk_query *q, int noisy, int want_var, int64_t *n_member, int64_t *n_other);
+/* one-shot: create(X) + plan + items_loo_multi + mix_multi + fetch_multi; Yq is N x R column-major with ldyq >= N;
+ * Vq == NULL: means only */
+int  pmk_predict_mixture_loo_multi(pmk_model *m, const pmk_kernel_desc *weight_th, const double *X, double radius,
+                                   double delta, int noisy, double *Yq, int64_t ldyq, double *Vq);
+/* the per-item results of pmk_query_items_multi, _multi_fitted or _loo_multi on the host: U[i * ldu + c] is mean c of item i
+ * (ldu >= R), v[i] its variance, items in the order of pmk_query_debug (per query: neighbours in hyperplane order, home
+ * last).  Either may be NULL; v must be NULL after a mean-only run (-3).  -2 if no multi-output items ran on this plan.
+ * Blocks. */
+int  pmk_query_get_items_multi(pmk_query *q, double *U, int64_t ldu, double *v);
 
 /* ---- per-patch kernels and noise ---------------------------------------------------------------------------------------
  * MixtureGPType carries one noise variance per patch (sigma2_set::Vector, mixtureGP.jl:44,114), and fitmixtureGP!

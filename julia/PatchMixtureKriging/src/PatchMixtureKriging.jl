@@ -21,7 +21,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
-       selectmixtureGP!, selectcandidates, loomixtureGP_blend
+       selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -720,6 +720,73 @@ function loomixtureGP_blend(Î·::MixtureGPType{Float64}, root, radius::Float64, Î
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end
     return Î¼, v, nm[], ns[]
+end
+
+"""loomixtureGP_blend_multi(Î·, root, radius, Î´, weight_Î¸, X; noisy = false, variance = true, items = false) -> (M, v): the
+leave-one-out of the BLENDED predictor for the R target columns of fitmixtureGPmulti!, with the trend of
+settrendmixtureGP! if one is set: M is N x R, v the N variances (nothing with variance = false: no strip kernel runs).
+Î·: built by MixtureGPType(root, X, Îµ), fitted, and solved (fitmixtureGPmulti! / settrendmixtureGP!); X: the same D x N
+matrix.  An item whose patch holds the point comes from the resident values (pmk_model_loo, run here), any other item is
+that of pmk_query_items_multi_fitted.  items = true runs the staged calls and returns
+(M, v, n_member, n_other, U, vi): U is R x total, the per-item means in the item order of the plan, vi their variances."""
+function loomixtureGP_blend_multi(Î·::MixtureGPType{Float64}, root, radius::Float64, Î´::Float64, weight_Î¸, X::Matrix{Float64};
+                                  noisy::Bool = false, variance::Bool = true, items::Bool = false)
+    Î·.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before loomixtureGP_blend_multi"))
+    Î·.N_global > 0 || throw(ArgumentError("this Î· was built from lists of patches: build it with MixtureGPType(root, X, Îµ)"))
+    R = Î·.R_multi
+    R >= 1 || throw(PMKError("fitmixtureGPmulti! must run before loomixtureGP_blend_multi"))
+    N = size(X, 2)
+    N == Î·.N_global || throw(ArgumentError("X has $N points, the model $(Î·.N_global)"))
+    M = Matrix{Float64}(undef, N, R); v = Vector{Float64}(undef, variance ? N : 0)
+    vp = variance ? pointer(v) : Ptr{Float64}(C_NULL)
+    check(ccall((:pmk_model_loo, libpmk), Cint, (Ptr{Cvoid},), Î·.model), "pmk_model_loo")
+    if !items
+        GC.@preserve v check(ccall((:pmk_predict_mixture_loo_multi, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Ptr{Float64}, Float64, Float64, Cint, Ptr{Float64}, Int64, Ptr{Float64}),
+                    Î·.model, Ref(desc(weight_Î¸)), X, radius, Î´, noisy ? 1 : 0, M, N, vp), "pmk_predict_mixture_loo_multi")
+        return M, (variance ? v : nothing)
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL); nm = Ref{Int64}(0); no = Ref{Int64}(0); total = Ref{Int64}(0)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), Î·.model, N, X, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, Î´), "pmk_query_plan")
+        check(ccall((:pmk_query_counts, libpmk), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}), q[], total,
+                    Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL)), "pmk_query_counts")
+        check(ccall((:pmk_query_items_loo_multi, libpmk), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{Int64}, Ref{Int64}), q[],
+                    noisy ? 1 : 0, variance ? 1 : 0, nm, no), "pmk_query_items_loo_multi")
+        check(ccall((:pmk_query_mix_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_Î¸)), 0, N),
+              "pmk_query_mix_multi")
+        GC.@preserve v check(ccall((:pmk_query_fetch_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], M, N, vp),
+                             "pmk_query_fetch_multi")
+        U = Matrix{Float64}(undef, R, total[]); vi = Vector{Float64}(undef, variance ? total[] : 0)
+        vip = variance ? pointer(vi) : Ptr{Float64}(C_NULL)
+        GC.@preserve vi check(ccall((:pmk_query_get_items_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], U, R,
+                                    vip), "pmk_query_get_items_multi")
+        return M, (variance ? v : nothing), nm[], no[], U, (variance ? vi : nothing)
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""selectblendGP_multi!(Î·, root, Y, candidates, X) -> (scores, best): score blending settings by the leave-one-out log
+pseudo-likelihood of the blended predictor.  candidates: a vector of (radius, Î´, weight_Î¸); Y: the N x R global targets the
+model holds; scores[g, c] = Î£â±¼ [-Â½ log vâ±¼ - (Y[j, c] - M_g[j, c])Â² / (2 vâ±¼) - Â½ log 2Ï€] with the noisy variances; best is
+the first argmax of the row sums, a row with a NaN never wins.  The fit is not touched."""
+function selectblendGP_multi!(Î·::MixtureGPType{Float64}, root, Y::Matrix{Float64}, candidates::Vector, X::Matrix{Float64})
+    isempty(candidates) && throw(ArgumentError("no candidates"))
+    R = Î·.R_multi
+    size(Y) == (size(X, 2), R) || throw(ArgumentError("Y must be N x R with the model's R = $R target columns"))
+    scores = Matrix{Float64}(undef, length(candidates), R)
+    for (g, (radius, Î´, weight_Î¸)) in enumerate(candidates)
+        M, v = loomixtureGP_blend_multi(Î·, root, Float64(radius), Float64(Î´), weight_Î¸, X; noisy = true)
+        for c = 1:R
+            scores[g, c] = sum(-0.5 .* log.(v) .- (Y[:, c] .- M[:, c]) .^ 2 ./ (2.0 .* v) .- 0.5 * log(2Ï€))
+        end
+    end
+    rows = vec(sum(scores, dims = 2))
+    valid = findall(!isnan, rows)
+    isempty(valid) && throw(ArgumentError("every candidate scored NaN"))
+    return scores, valid[argmax(rows[valid])]
 end
 
 # ------------------------------------------------------------------------------------------ kriging with a trend

@@ -148,6 +148,9 @@ SIGNATURES = {
     "pmk_model_get_loo_multi": (C.c_int, [_vp, _dpp, _ip, _dpp]),
     "pmk_query_items_loo": (C.c_int, [_vp, C.c_int, _ip, _ip]),
     "pmk_predict_mixture_loo": (C.c_int, [_vp, _kp, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp]),
+    "pmk_query_items_loo_multi": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip]),
+    "pmk_predict_mixture_loo_multi": (C.c_int, [_vp, _kp, _dp, C.c_double, C.c_double, C.c_int, _dp, C.c_int64, _dp]),
+    "pmk_query_get_items_multi": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
     "pmk_model_set_trend": (C.c_int, [_vp, C.c_int]),
     "pmk_model_get_trend": (C.c_int, [_vp, C.POINTER(C.c_int), _dp, _dp]),
     "pmk_model_trend_info": (C.c_int, [_vp, _i32p]),

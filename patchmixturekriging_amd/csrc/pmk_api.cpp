@@ -2101,6 +2101,130 @@ int pmk_predict_mixture_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------ blended leave-one-out, R columns
+// loo_model_ok plus the multi-output state; host state only
+static int loo_multi_model_ok(const pmk_model *m, int64_t Nq, const char *who)
+{
+    if (int rc = loo_model_ok(m, Nq, who)) return rc;
+    if (!m->multi_solved) { set_error("%s: pmk_model_solve_multi has not run on the resident factor", who); return -3; }
+    return 0;
+}
+
+int pmk_query_items_loo_multi(pmk_query *q, int noisy, int want_var, int64_t *n_member, int64_t *n_other)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_loo_multi: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (int rc = loo_multi_model_ok(m, q->Nq, "pmk_query_items_loo_multi")) return rc;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int R = m->R_multi, qt = m->trend_q;
+    int rc;
+    int64_t ns = 0;
+    noisy = noisy != 0;
+    want_var = want_var != 0;
+    q->R_items = 0;
+    q->mixed_multi = false;
+    if (q->um_cap < q->total * (R + qt)) {
+        PMK_HIP(hipStreamSynchronize(s));       // earlier launches may still read the buffer replaced below
+        dev_free(q->d_um);
+        q->um_cap = 0;
+        if (dev_alloc(&q->d_um, q->total * (R + qt))) return -100;
+        q->um_cap = q->total * (R + qt);
+    }
+    q->R_items = R;
+    q->um_ld = R + qt;
+    c->tic("loo_items_multi");
+    if (q->total > 0) {
+        if ((rc = loo_reserve(q, q->total))) { q->R_items = 0; return rc; }
+        // members: a lookup per item, and the marks of the rest
+        if ((rc = PMK_BY_DTYPE(m, launch_loo_member_multi(q, noisy, want_var, q->d_loo_mark, s)))) { q->R_items = 0; return rc; }
+        if (exclusive_scan_i32_to_i64(q->d_loo_mark, q->d_loo_off, q->total, &q->d_tmp, &q->tmp_bytes, s)) {
+            set_error("pmk_query_items_loo_multi: prefix scan failed");
+            q->R_items = 0;
+            return -100;
+        }
+        PMK_HIP(hipMemcpyAsync(&ns, q->d_loo_off + q->total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        PMK_HIP(hipStreamSynchronize(s));
+    }
+    if (ns > 0) {
+        // non-members: the items of pmk_query_items_multi_fitted, as explicit items of the inner query
+        rc = 0;
+        if (!q->loo_inner) rc = pmk_query_create(m, 0, nullptr, &q->loo_inner);
+        pmk_query *in = q->loo_inner;
+        if (!rc)
+            rc = PMK_BY_DTYPE(m, launch_loo_compact(q, q->d_loo_mark, q->d_loo_off, q->d_loo_x, q->d_loo_region, q->d_loo_diag, s));
+        if (!rc) rc = query_set_items(in, ns, q->d_loo_x, q->d_loo_region);
+        if (!rc) {
+            // the addends in request order = the inner query's item order; borrowed for this launch only (the arena is q's)
+            in->d_qdiag = q->d_qdiag ? q->d_loo_diag : nullptr;
+            in->min_v = q->min_v;
+            rc = pmk_query_items_multi_fitted(in, want_var);
+            in->d_qdiag = nullptr;
+        }
+        if (!rc) rc = launch_loo_scatter_multi(q, in, noisy, want_var, q->d_loo_mark, q->d_loo_off, s);
+        if (rc) { q->R_items = 0; return rc; }
+    }
+    c->toc("loo_items_multi");
+    q->var_items = want_var != 0;
+    if (n_member) *n_member = q->total - ns;
+    if (n_other) *n_other = ns;
+    return 0;
+}
+
+int pmk_predict_mixture_loo_multi(pmk_model *m, const pmk_kernel_desc *weight_th, const double *X, double radius, double delta,
+                                  int noisy, double *Yq, int64_t ldyq, double *Vq)
+{
+    if (!m) { set_error("pmk_predict_mixture_loo_multi: model is NULL"); return -1; }
+    int rc = loo_multi_model_ok(m, m->N_global, "pmk_predict_mixture_loo_multi");
+    if (rc) return rc;
+    if (!X) { set_error("pmk_predict_mixture_loo_multi: X is NULL"); return -2; }
+    if (Yq && ldyq < m->N_global) {
+        set_error("pmk_predict_mixture_loo_multi: ldyq = %lld < N = %lld", (long long)ldyq, (long long)m->N_global);
+        return -4;
+    }
+    pmk_query *q = nullptr;
+    if ((rc = pmk_query_create(m, m->N_global, X, &q))) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_loo_multi(q, noisy, Vq != nullptr, nullptr, nullptr)) &&
+        !(rc = pmk_query_mix_multi(q, weight_th, 0, q->Nq)))
+        rc = pmk_query_fetch_multi(q, Yq, ldyq, Vq);
+    pmk_query_destroy(q);
+    return rc;
+}
+
+int pmk_query_get_items_multi(pmk_query *q, double *U, int64_t ldu, double *v)
+{
+    if (!q || !q->planned) { set_error("pmk_query_get_items_multi: query is not planned"); return -1; }
+    if (q->R_items < 1) { set_error("pmk_query_get_items_multi: pmk_query_items_multi has not run on this plan"); return -2; }
+    if (v && !q->var_items) {
+        set_error("pmk_query_get_items_multi: v was not computed (the items ran with want_var = 0)");
+        return -3;
+    }
+    if (U && ldu < q->R_items) {
+        set_error("pmk_query_get_items_multi: ldu = %lld < R = %d", (long long)ldu, q->R_items);
+        return -4;
+    }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    const size_t T = (size_t)q->total, R = (size_t)q->R_items, ld = (size_t)q->um_ld;
+    if (T == 0 || (!U && !v)) return 0;
+    std::vector<int32_t> pos(T);
+    PMK_HIP(hipMemcpy(pos.data(), q->d_item_pos, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
+    if (U) {
+        std::vector<double> tmp(T * ld);
+        PMK_HIP(hipMemcpy(tmp.data(), q->d_um, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < T; ++i)
+            for (size_t j = 0; j < R; ++j) U[i * (size_t)ldu + j] = tmp[(size_t)pos[i] * ld + j];
+    }
+    if (v) {
+        std::vector<double> tmp(T);
+        PMK_HIP(hipMemcpy(tmp.data(), q->d_v, sizeof(double) * T, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < T; ++i) v[i] = tmp[(size_t)pos[i]];
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ model selection
 static int evidence_common(pmk_model *m, int R, double *logdet, double *quad)
 {

@@ -14,6 +14,9 @@ namespace pmk {
 constexpr int TILE = 128;       // factorisation tile edge; slabs are padded to a multiple of it
 constexpr int MAX_D = 4;        // input dimension limit (the reference's examples use 1, 2 and 3)
 constexpr int TQ = 256;         // query columns per prediction strip (8 waves x 32)
+// layout of the per-patch trend state and of the multi-output blocks, shared by pmk_trend.hip and pmk_loo_mix_multi.hip
+constexpr int TQ_MAX = 1 + MAX_D;             // basis functions of the linear trend at D = 4; leading dimension of L_G
+constexpr int TR_RP = PMK_MAX_OUTPUTS;        // columns of a row of the target / weight block
 
 void set_error(const char *fmt, ...);
 
@@ -224,6 +227,9 @@ struct pmk_query {
 
 namespace pmk {
 
+// sigma2 of the resident factor per local patch: the device array after pmk_model_fit_patches, one value otherwise
+inline const double *patch_sigma2s(const pmk_model *m) { return m->hyper_uniform ? nullptr : m->d_sigma2s; }
+
 // ---- launchers implemented in the .hip files (all enqueue on `s`) ----
 // precision-generic kernels live in namespaces f64 / f32 (the same sources compiled twice)
 // launch_kernel_matrix_slabs, launch_items, launch_items_multi: th non-null is that descriptor for every patch, null the
@@ -254,6 +260,7 @@ namespace pmk {
                            int32_t *region_out, double *diag_out, hipStream_t s);                                    \
     int launch_loo_scatter(pmk_query *q, int noisy, const int32_t *d_mark, const int64_t *d_off, const double *d_ru, \
                            const double *d_rv, hipStream_t s);                                                       \
+    int launch_loo_member_multi(pmk_query *q, int noisy, int want_var, int32_t *d_mark, hipStream_t s);              \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -274,6 +281,8 @@ int launch_sort_items(pmk_query *q, hipStream_t s);
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s);
+int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
+                             const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);
 int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s);
 int launch_export_results(pmk_query *q, double *u_out, double *v_out, hipStream_t s);

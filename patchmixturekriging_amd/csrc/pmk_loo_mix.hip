@@ -110,9 +110,6 @@ __global__ __launch_bounds__(256) void loo_scatter_kernel(int64_t total, const i
     v_out[k] = v;
 }
 
-// sigma2 of the resident factor per local patch: the device array after pmk_model_fit_patches, one value otherwise
-static const double *patch_sigma2s(const pmk_model *m) { return m->hyper_uniform ? nullptr : m->d_sigma2s; }
-
 int launch_loo_member(pmk_query *q, int noisy, int32_t *d_mark, hipStream_t s)
 {
     const pmk_model *m = q->m;

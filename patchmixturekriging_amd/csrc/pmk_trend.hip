@@ -29,8 +29,7 @@
 
 namespace pmk {
 
-constexpr int TQ_MAX = 1 + MAX_D;             // basis functions of the linear trend at D = 4
-constexpr int TR_RP = PMK_MAX_OUTPUTS;        // columns of a block
+// TQ_MAX and TR_RP: pmk_internal.h
 constexpr int TR_BETA = TQ_MAX * TR_RP;       // doubles of beta per patch
 constexpr int TR_G = TQ_MAX * TQ_MAX;         // doubles of G and of L_G per patch
 

@@ -540,6 +540,7 @@ class DeviceQuery:
         t, f, o = C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pmk_query_counts(self.h, C.byref(t), C.byref(f), C.byref(o)))
         self.total, self.first_owned, self.num_owned = t.value, f.value, o.value
+        self.R_items = 0                    # a new plan discards the items, as in the library
         return self.total
 
     def region_offsets(self, P_global):
@@ -577,12 +578,48 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_items_loo(self.h, int(bool(noisy)), C.byref(nm), C.byref(ns)), "pmk_query_items_loo")
         return nm.value, ns.value
 
+    def items_loo_multi(self, noisy=False, variance=True):
+        """pmk_query_items_loo_multi: items_loo for the R target columns of the multi-output path, with the model's trend
+        if it has one -> (n_member, n_other).  A member item is mu_c = Y[i, c] - C[i, c] / Q_ii with variance 1 / Q_ii
+        (- sigma2_r), Q the trend-aware diagonal of loo_values_multi(); any other item is items_multi_fitted's.
+        variance=False: means only, no strip kernel runs.  Follow with mix_multi() and fetch_multi()."""
+        m = self.model
+        if not getattr(m, "_from_tree", False):
+            raise _lib.PmkError("items_loo_multi: the model was built from lists of patches, not by from_tree")
+        if self.Nq != m.N:
+            raise _lib.PmkError("items_loo_multi: the query has %d points, the model %d: query j must be training point j"
+                                % (self.Nq, m.N))
+        if not getattr(m, "_all_leaves", False):
+            raise _lib.PmkError("items_loo_multi: the model holds a shard of the leaves; the blended leave-one-out needs all")
+        if not getattr(m, "_has_kernels", False):
+            raise _lib.PmkError("the model holds no kernels: fit it first")
+        m._need(loo=True)           # the library's order: a new fit makes both stale and is told about loo() first
+        m._need(multi=True)
+        nm, no = C.c_int64(), C.c_int64()
+        _lib.check(self.L.pmk_query_items_loo_multi(self.h, int(bool(noisy)), int(bool(variance)), C.byref(nm), C.byref(no)),
+                   "pmk_query_items_loo_multi")
+        self.variance, self.R_items = bool(variance), int(m.R)
+        return nm.value, no.value
+
+    def item_values_multi(self):
+        """pmk_query_get_items_multi -> (U [total, R], v [total] or None after a mean-only run): the per-item results of
+        items_multi, items_multi_fitted or items_loo_multi in the item order of debug()"""
+        R = getattr(self, "R_items", 0)         # the R of the items run: the library writes that many columns
+        if R < 1:
+            raise _lib.PmkError("item_values_multi: no items_multi, items_multi_fitted or items_loo_multi has run")
+        T = max(int(self.total), 1)
+        U = np.empty((T, R))
+        v = np.empty(T) if getattr(self, "variance", False) else None
+        _lib.check(self.L.pmk_query_get_items_multi(self.h, _d(U), R, None if v is None else _d(v)),
+                   "pmk_query_get_items_multi")
+        return U[:self.total], (None if v is None else v[:self.total])
+
     def items_multi_fitted(self, variance=True):
         """pmk_query_items_multi_fitted: items_multi with the model's own kernels"""
         if not getattr(self.model, "_has_kernels", False):
             raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
         _lib.check(self.L.pmk_query_items_multi_fitted(self.h, int(bool(variance))), "pmk_query_items_multi_fitted")
-        self.variance = bool(variance)
+        self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
 
     def item_buffers(self):
         u, v = C.c_void_p(), C.c_void_p()
@@ -650,7 +687,7 @@ class DeviceQuery:
     def items_multi(self, theta, variance=True):
         d = theta.desc()
         _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
-        self.variance = bool(variance)
+        self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
 
     def mix_multi(self, weight_theta, q0=0, q1=None):
         d = weight_theta.desc()
@@ -1244,3 +1281,59 @@ def selectblendGP_(eta, root, y, candidates, X=None):
     if len(valid) == 0:
         raise ValueError("every candidate scored NaN")
     return scores, int(valid[int(np.argmax(scores[valid]))])
+
+
+# ---- the same for the multi-output path: R target columns, with or without a trend (fitmixtureGP_multi_ / _trend_)
+def _blend_multi_model(eta, who):
+    model = _blend_model(eta, who)
+    if not getattr(model, "_multi_solved", False):
+        raise _lib.PmkError("%s: fitmixtureGP_multi_ or fitmixtureGP_trend_ must run first (solve_multi has not run on the "
+                            "resident factor)" % who)
+    return model
+
+
+def loomixtureGP_blend_multi(eta, root, radius, delta, weight_theta, X=None, noisy=False, variance=True):
+    """loomixtureGP_blend for the R target columns of fitmixtureGP_multi_ or fitmixtureGP_trend_ -> (MU [N, R], var [N] or
+    None): what querymixtureGP_multi_patches would predict at training point j had the model, trend included, been fitted
+    without j, the tree held fixed.  No refit.  eta: built by MixtureGPType.from_tree; X, noisy as loomixtureGP_blend.
+    variance=False: means only (no strip kernel runs anywhere).  Runs loo() if it is stale."""
+    model = _blend_multi_model(eta, "loomixtureGP_blend_multi")
+    q = _blend_query(model, X, "loomixtureGP_blend_multi")
+    if not model._loo_done:
+        model.loo()
+    q.plan(radius, delta)
+    q.items_loo_multi(noisy, variance)
+    q.mix_multi(weight_theta)
+    return q.fetch_multi(model.R)
+
+
+def selectblendGP_multi_(eta, root, Y, candidates, X=None):
+    """selectblendGP_ for R target columns -> (scores [G, R], best).  candidates: a list of (radius, delta, weight_theta);
+    scores[g, c] = loo_log_pseudo_likelihood(Y[:, c] - MU_g[:, c], var_g) with the noisy variances, Y the (N, R) global
+    targets the model holds; best = the first argmax of the row sums, a row with a NaN never wins, all-NaN raises
+    ValueError.  One query object, re-planned per candidate; the fit is not touched."""
+    candidates = list(candidates)
+    if not candidates:
+        raise ValueError("no candidates")
+    model = _blend_multi_model(eta, "selectblendGP_multi_")
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.shape != (model.N, model.R):
+        raise ValueError("Y must hold the %d x %d global targets" % (model.N, model.R))
+    q = _blend_query(model, X, "selectblendGP_multi_")
+    if not model._loo_done:
+        model.loo()
+    scores = np.empty((len(candidates), model.R))
+    for g, (radius, delta, weight_theta) in enumerate(candidates):
+        q.plan(radius, delta)
+        q.items_loo_multi(True, True)
+        q.mix_multi(weight_theta)
+        MU, var = q.fetch_multi(model.R)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scores[g] = [loo_log_pseudo_likelihood(Y[:, c] - MU[:, c], var) for c in range(model.R)]
+    rows = scores.sum(axis=1)
+    valid = np.nonzero(~np.isnan(rows))[0]
+    if len(valid) == 0:
+        raise ValueError("every candidate scored NaN")
+    return scores, int(valid[int(np.argmax(rows[valid]))])
