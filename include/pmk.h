@@ -359,7 +359,10 @@ int  pmk_model_loo(pmk_model *m);
 /* blocks. res[r][i] = c_i / d_i (= y_i - mu_-i, so mu_-i = y_i - res[r][i]) from the weights resident at the time of the
  * call, var[r][i] = 1 / d_i (includes sigma2).  Either may be NULL. */
 int  pmk_model_get_loo(pmk_model *m, double *const *res, double *const *var);
-/* R columns: RES[r] is n[r] x R column-major, leading dimension ldres[r] >= n[r]; var is shared by the columns */
+/* R columns: RES[r] is n[r] x R column-major, leading dimension ldres[r] >= n[r]; var is shared by the columns.
+ * With a trend of q basis functions, a patch of n_r <= q points returns NaN in RES and var: leaving one point out leaves
+ * fewer points than basis functions, so no leave-one-out prediction exists (at n_r == q the fit itself is fine, tinfo is
+ * 0 and Q_ii is 0 up to rounding).  beta, the weights and ordinary queries of such a patch are unchanged. */
 int  pmk_model_get_loo_multi(pmk_model *m, double *const *RES, const int64_t *ldres, double *const *var);
 
 /* ---- blended leave-one-out: cross-validate the MIXTURE predictor, no refits ---------------------------------------------
@@ -404,7 +407,10 @@ int  pmk_predict_mixture_loo(pmk_model *m, const pmk_kernel_desc *weight_th, con
  *     forward substitution of the per-patch values: what numpy computes from pmk_model_get_loo_multi's RES and var.
  *   non-member:  the item of pmk_query_items_multi_fitted for that (point, region), the same bits: mu_c with h(x)^T beta_c
  *     added, v with the trend term added after the clamp; with noisy, sigma2_r is added with one add after that.
- * NaN in every column and in v for a patch with info != 0 or, with a trend, tinfo != 0.  In 1 / Q - sigma2 the cancellation
+ * NaN in every column and in v for a patch with info != 0 or, with a trend, tinfo != 0.  With a trend of q basis functions
+ * a MEMBER item of a patch of n_r <= q points is NaN in every column and in v as well (no leave-one-out prediction from
+ * fewer than q points, as in pmk_model_get_loo_multi); a non-member item of a patch of n_r == q points stays the fitted
+ * predictor's, bit for bit.  In 1 / Q - sigma2 the cancellation
  * is that of the single-output form, with the leverage of the point under the trend model; clamped at min_v.
  * want_var = 0: means only; no strip kernel runs anywhere, v is not computed and pmk_query_fetch_multi refuses Vq.
  * After pmk_query_plan, instead of pmk_query_items_multi*; pmk_query_mix_multi, pmk_query_fetch_multi(_dev) and

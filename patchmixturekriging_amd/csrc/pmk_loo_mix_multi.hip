@@ -64,7 +64,8 @@ __global__ __launch_bounds__(256) void loo_member_multi_kernel(int64_t total, co
     mark[k] = 0;
     const int64_t e = descs[p].yoff + (lo - base);
     const int64_t row = e * TR_RP;
-    const bool bad = info[p] != 0 || (tinfo && tinfo[p] != 0);
+    // n <= q: the point left out, fewer points remain than basis functions (trend_loo_values_kernel's rule)
+    const bool bad = info[p] != 0 || (tinfo && tinfo[p] != 0) || (q > 0 && descs[p].n <= q);
     const double nan = __builtin_nan("");
     double z[TQ_MAX], s = 0.0;
     const double *L = Lg ? Lg + (int64_t)p * (TQ_MAX * TQ_MAX) : nullptr;      // null exactly when q == 0

@@ -183,7 +183,8 @@ __global__ __launch_bounds__(256) void trend_loo_values_kernel(const PatchDesc *
 {
     const int r = blockIdx.x;
     const PatchDesc pd = descs[r];
-    const bool bad = info[r] != 0 || tinfo[r] != 0;
+    // n <= q: leaving one point out leaves fewer points than basis functions, no such prediction (Q_ii is rounding noise)
+    const bool bad = info[r] != 0 || tinfo[r] != 0 || (q > 0 && pd.n <= q);
     const double nan = __builtin_nan("");
     const double *L = Lg + (int64_t)r * TR_G;
     for (int i = threadIdx.x; i < pd.n; i += 256) {

@@ -450,7 +450,8 @@ class DeviceModel:
 
     def loo_values_multi(self):
         """pmk_model_get_loo_multi -> (RES, var): RES[r] is n_r x R (one residual column per target column), var is
-        shared by the columns"""
+        shared by the columns.  With a trend of q basis functions a patch of n_r <= q points returns NaN in both: leaving
+        one point out leaves fewer points than basis functions"""
         self._need(loo=True, multi=True)
         RES = [np.empty((int(n), self.R), order="F") for n in self.n]
         var = [np.empty(int(n)) for n in self.n]
@@ -582,6 +583,8 @@ class DeviceQuery:
         """pmk_query_items_loo_multi: items_loo for the R target columns of the multi-output path, with the model's trend
         if it has one -> (n_member, n_other).  A member item is mu_c = Y[i, c] - C[i, c] / Q_ii with variance 1 / Q_ii
         (- sigma2_r), Q the trend-aware diagonal of loo_values_multi(); any other item is items_multi_fitted's.
+        With a trend of q basis functions a member item of a patch of n <= q points is NaN (means and variance): no
+        leave-one-out prediction exists from fewer than q points; a non-member item of such a patch stays valid.
         variance=False: means only, no strip kernel runs.  Follow with mix_multi() and fetch_multi()."""
         m = self.model
         if not getattr(m, "_from_tree", False):
@@ -1296,7 +1299,9 @@ def loomixtureGP_blend_multi(eta, root, radius, delta, weight_theta, X=None, noi
     """loomixtureGP_blend for the R target columns of fitmixtureGP_multi_ or fitmixtureGP_trend_ -> (MU [N, R], var [N] or
     None): what querymixtureGP_multi_patches would predict at training point j had the model, trend included, been fitted
     without j, the tree held fixed.  No refit.  eta: built by MixtureGPType.from_tree; X, noisy as loomixtureGP_blend.
-    variance=False: means only (no strip kernel runs anywhere).  Runs loo() if it is stale."""
+    variance=False: means only (no strip kernel runs anywhere).  Runs loo() if it is stale.
+    With a trend of q basis functions, a point that is a member of a patch of n <= q points gets NaN in its row of MU and
+    in var: without it the patch has fewer points than basis functions, so the prediction does not exist."""
     model = _blend_multi_model(eta, "loomixtureGP_blend_multi")
     q = _blend_query(model, X, "loomixtureGP_blend_multi")
     if not model._loo_done:

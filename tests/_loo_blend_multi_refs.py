@@ -13,7 +13,10 @@ tests/test_gpu_loo_blend_multi.py): R target columns on the workload of tests/_l
                   long-double refit of a 200-point patch takes 55 ms and the three cases need 1388 of them per trend, so
                   those of the members are RECORDED in tests/golden/loo_blend_multi_refits.npz (written by
                   tests/golden/make_loo_blend_multi.py from this module, rounded to double); an entry the file does not
-                  hold is computed here.
+                  hold is computed here.  The file serves the workload it was recorded from and no other
+                  (MultiOracle.is_recorded_workload): its keys name eps and the trend only.
+
+MultiOracle takes the tree depth as an argument (default: the base workload's) and the dimension from X.
 
 Every item function returns, per point, (ts, U [k, R], v [k]) in reference order (neighbours in hyperplane order, the home
 item last); blend() mixes them per column with _loo_blend_refs.blend_items.
@@ -51,6 +54,16 @@ def targets(R=3):
     return X, Y
 
 
+_GOLDEN_WORKLOAD = []
+
+
+def _golden_workload():
+    """(X, Y) the recorded refits were made from, generated once"""
+    if not _GOLDEN_WORKLOAD:
+        _GOLDEN_WORKLOAD.append(targets(GOLDEN_R))
+    return _GOLDEN_WORKLOAD[0]
+
+
 def basis(X, trend):
     X = np.atleast_2d(X)
     return np.zeros((X.shape[0], 0)) if trend is None else TR.basis(X, trend)
@@ -78,8 +91,8 @@ def predict_fp64(ref, Kq, kqq, Hq):
 class MultiOracle(BR.Oracle):
     """the oracle's view of one multi-output model: Y (N, R), trend None / "constant" / "linear", hyper as Oracle"""
 
-    def __init__(self, X, Y, eps, hyper, trend):
-        super().__init__(X, np.ascontiguousarray(Y[:, 0]), eps, hyper)
+    def __init__(self, X, Y, eps, hyper, trend, levels=BR.LEVELS):
+        super().__init__(X, np.ascontiguousarray(Y[:, 0]), eps, hyper, levels)
         self.Y, self.trend, self.R = np.asarray(Y), trend, Y.shape[1]
         self._fit64, self._fitref, self._refit = {}, {}, {}
         self._golden = None
@@ -145,10 +158,20 @@ class MultiOracle(BR.Oracle):
     def golden_key(self):
         return "eps%g_%s" % (self.eps, self.trend)
 
+    def is_recorded_workload(self):
+        """the recorded refits belong to ONE workload: targets(GOLDEN_R) under a tree of BR.LEVELS levels, fitted with
+        BR.A and BR.SIGMA2.  N, D, the levels, the hyperparameters and every bit of X and Y must be that workload's; any
+        other one computes its refits (the (r, j) pairs alone do not tell two workloads apart)"""
+        if not (self.uniform and self.R == GOLDEN_R and self.levels == BR.LEVELS and self.X.shape == (BR.N, BR.D)
+                and self.hyper[0] == (("s34", BR.A), BR.SIGMA2)):
+            return False
+        Xg, Yg = _golden_workload()
+        return bool(np.array_equal(self.X, Xg) and np.array_equal(self.Y, Yg))
+
     def _recorded(self):
         if self._golden is None:
             self._golden = {}
-            if self.trend is not None and self.uniform and self.R == GOLDEN_R and os.path.exists(GOLDEN):
+            if self.trend is not None and self.is_recorded_workload() and os.path.exists(GOLDEN):
                 z, k = np.load(GOLDEN), self.golden_key()
                 if k + "_rj" in z.files:
                     self._golden = {(int(a), int(b)): (z[k + "_mu"][n], float(z[k + "_v"][n]))

@@ -50,11 +50,12 @@ def blend_items(wth, ts, us, vs):
 
 class Oracle:
     """the oracle's view of one model: tree of X, index lists for eps (None: the tree's leaves), fits with hyper[r] =
-    ((family, a), sigma2) per patch"""
+    ((family, a), sigma2) per patch.  The tree has `levels` levels (2^(levels - 1) leaves); the dimension is X's"""
 
-    def __init__(self, X, y, eps, hyper):
-        self.X, self.y, self.eps = X, y, eps
-        self.bsp = O.BSP(X, LEVELS)
+    def __init__(self, X, y, eps, hyper, levels=LEVELS):
+        self.X, self.y, self.eps, self.levels = X, y, eps, levels
+        self.D = X.shape[1]
+        self.bsp = O.BSP(X, levels)
         self.P = self.bsp.P
         if eps is None:
             off, inds = self.bsp.leaves()
@@ -82,7 +83,7 @@ class Oracle:
 
     def k0(self):
         """largest k(x, x) of the patches' kernels (1 for every stationary family used here)"""
-        z = np.zeros(D)
+        z = np.zeros(self.D)
         return max(O.kernel_eval(th, z, z) for th in self.th)
 
     def row_of(self, r, j):

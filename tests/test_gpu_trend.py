@@ -214,10 +214,12 @@ def test_against_long_double_reference(trend, dtype):
             "v_near": (v[:-2], v_f[:-2], v_ld[:-2]), "v_far": (v[-2:], v_f[-2:], v_ld[-2:]),
         }
         # C = C_Y - C_H beta cancels (to exactly zero for one point and a constant trend): the scale of its error is that
-        # of its terms.  Leaving one of n <= q points out leaves fewer points than basis functions: no such prediction.
+        # of its terms.  Leaving one of n <= q points out leaves fewer points than basis functions: no such prediction,
+        # and the library says so with NaN.
         scales = {"weights": float(np.abs(ld["C_Y"]).max() + np.abs(ld["C_H"] @ ld["beta"]).max())}
         if len(Xs[r]) <= Q_OF[trend](Xs[r].shape[1]):
             del figures["loo_res"], figures["loo_var"]
+            assert np.isnan(RES[r]).all() and np.isnan(VAR[r]).all(), (r, RES[r], VAR[r])
         for name, (dev, f64, ref_ld) in figures.items():
             unit = ref["kappa"] * u * scales.get(name, float(np.abs(ref_ld).max()))
             d, s = _err(dev, ref_ld) / unit, _err(f64, ref_ld) / unit
