@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -494,6 +494,45 @@ int  pmk_model_set_diag_global(pmk_model *m, const double *diag);
  * no host synchronisation.  Same argument rules as the host forms (Vq_dev must be NULL after a mean-only items_multi). */
 int  pmk_query_fetch_dev(pmk_query *q, double *Yq_dev, double *Vq_dev);
 int  pmk_query_fetch_multi_dev(pmk_query *q, double *Yq_dev, int64_t ldyq, double *Vq_dev);
+
+/* ---- gradient of the blended mean of the multi-output path (R columns, with or without a trend; fp64 and fp32 models) ---
+ * For every stationary family grad_x k(x, z) = psi(tau) (x - z) with psi = phi'(tau) / tau, finite at tau = 0.  Per item
+ * (query x, region r) and column c:  G[d + D c] = sum_k psi(|x - z_k|) (x_d - z_{k,d}) C_r[k, c], plus beta_r[1 + d, c]
+ * with a linear trend (a constant trend adds nothing).  With w_i = phi_w(|t_i|) (home: w = 1), S = sum_i w_i and
+ * Y_c = sum_i w_i u_{i,c} / S, in the item order of pmk_query_mix_multi:
+ *   dY_c/dx_d = (1 / S) sum_i [ w_i G_{i,d,c} + (u_{i,c} - Y_c) dw_i/dx_d ],
+ *   dw_i/dx_d = -psi_w(|t_i|) t_i v_{plane(i),d} for a neighbour (t = c - v . x of the hyperplane the plan accepted the
+ *   item at), 0 for the home item.
+ * This is the derivative with the ITEM LIST HELD FIXED.  Where the list changes the blend itself jumps -- at the radius
+ * cut-off unless phi_w vanishes there, at a delta test, and where the home leaf changes -- and no derivative exists there.
+ * A patch with info != 0, or tinfo != 0 under a trend, gives NaN in all D R values of its items and in every query that
+ * blends one of them.  The gradient of the variance is not provided.  Not available through the sharded / all-gather
+ * exchanges; the model must hold every leaf.  Stage timers "items_grad" and "mix_grad".  A new plan discards the gradients,
+ * as it does the items. */
+/* per-item gradients of the items that pmk_query_items_multi or _multi_fitted last computed on this plan.  th: the kernel
+ * for every patch, or NULL for the model's own kernels (-3 if it holds none).  Enqueues only.  -1: no plan; -2: the last
+ * items on this plan are not those of pmk_query_items_multi / _multi_fitted (none yet, or pmk_query_items_loo_multi, whose
+ * member items are lookups and not functions of x), a Brownian-bridge family (not differentiable on the diagonal; the text
+ * names the family), or PMK_MODSQEXP with D > 1; -3: the multi-output weights are stale (pmk_model_solve_multi has not run
+ * on the resident factor: a new fit, pmk_model_set_targets_multi* and pmk_model_set_trend each make them stale). */
+int  pmk_query_items_grad(pmk_query *q, const pmk_kernel_desc *th);
+/* the gradient of the blend for queries [q0, q1), weight_th as in pmk_query_mix_multi (a Brownian-bridge weight kernel:
+ * -2).  Enqueues.  -2 before pmk_query_items_grad has run on this plan. */
+int  pmk_query_mix_grad(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1);
+/* blocks; dYq[j + lddy * (d + D * c)] = dY_c/dx_d at query j, lddy >= Nq.  -2 before pmk_query_mix_grad. */
+int  pmk_query_fetch_grad(pmk_query *q, double *dYq, int64_t lddy);
+/* the same into a DEVICE array: device-to-device on the context's stream, no host synchronisation */
+int  pmk_query_fetch_grad_dev(pmk_query *q, double *dYq_dev, int64_t lddy);
+/* the per-item gradients G[i * ldg + d + D * c] (ldg >= D R) and the hyperplane of every item (plane[i]: the pre-order
+ * index into hp_v / hp_c of pmk_bsp_arrays for a neighbour item, -1 for a home item and for every item of
+ * pmk_query_create_items), items in the order of pmk_query_debug.  Either pointer may be NULL; G needs
+ * pmk_query_items_grad (-2).  Blocks. */
+int  pmk_query_get_items_grad(pmk_query *q, double *G, int64_t ldg, int32_t *plane);
+/* one-shot: create + plan + mean-only pmk_query_items_multi_fitted + pmk_query_items_grad(NULL) + pmk_query_mix_multi +
+ * pmk_query_mix_grad + both fetches; no strip kernel runs anywhere on this path.  Yq: Nq x R column-major, ldyq >= Nq
+ * (may be NULL); dYq as in pmk_query_fetch_grad (may be NULL). */
+int  pmk_predict_mixture_grad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                     double radius, double delta, double *Yq, int64_t ldyq, double *dYq, int64_t lddy);
 
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,

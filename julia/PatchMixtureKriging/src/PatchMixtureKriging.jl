@@ -21,7 +21,8 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        MixtureGPType, MixtureGPDebugType, fitmixtureGP!, fitmixtureGPmulti!, querymixtureGPmulti!,
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
-       selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!
+       selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
+       querymixtureGP_grad
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -927,6 +928,52 @@ function querymixtureGPmulti!(Yq::Matrix{T}, Vq::Union{Vector{T},Nothing}, Xq::V
                 Vq === nothing ? Ptr{Float64}(C_NULL) : pointer(Vq)), "pmk_predict_mixture_multi_fitted")
     Yq .= view(Ym, :, 1:size(Yq, 2))
     return nothing
+end
+
+"""querymixtureGP_grad(Xq, η, root, levels, radius, δ, weight_θ; items = false) -> (Yq, dYq): the blended mean of the R
+target columns (Nq x R) and its gradient, dYq[j, d, c] = ∂Y_c/∂x_d at query j (Nq x D x R), with the model's own kernels
+and its trend if one is set (pmk_predict_mixture_grad_fitted).  The derivative holds the item list of each query fixed:
+where that list changes (the radius cut-off, a δ test, a change of home leaf) the blend itself jumps.  Brownian-bridge
+kernels are refused.  items = true runs the staged calls and also returns (G, plane): G is D x R x total, the per-item
+gradients in the item order of the plan, plane the 1-based pre-order hyperplane of every neighbour item (0 for home)."""
+function querymixtureGP_grad(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float64}, root, levels, radius::Float64, δ::Float64,
+                             weight_θ; items::Bool = false)
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_grad"))
+    R = η.R_multi
+    R >= 1 || throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_grad"))
+    Nq = length(Xq); Xm = array2matrix(Xq); D = size(Xm, 1)
+    Yq = Matrix{Float64}(undef, Nq, R); dYq = Array{Float64,3}(undef, Nq, D, R)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    if !items
+        check(ccall((:pmk_predict_mixture_grad_fitted, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+                    η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Yq, max(Nq, 1), dYq, max(Nq, 1)),
+              "pmk_predict_mixture_grad_fitted")
+        return Yq, dYq
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL); total = Ref{Int64}(0)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_counts, libpmk), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}), q[], total,
+                    Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL)), "pmk_query_counts")
+        check(ccall((:pmk_query_items_multi_fitted, libpmk), Cint, (Ptr{Cvoid}, Cint), q[], 0), "pmk_query_items_multi_fitted")
+        check(ccall((:pmk_query_items_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}), q[], Ptr{KernelDesc}(C_NULL)),
+              "pmk_query_items_grad")
+        check(ccall((:pmk_query_mix_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_multi")
+        check(ccall((:pmk_query_mix_grad, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_grad")
+        check(ccall((:pmk_query_fetch_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], Yq, max(Nq, 1),
+                    Ptr{Float64}(C_NULL)), "pmk_query_fetch_multi")
+        check(ccall((:pmk_query_fetch_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], dYq, max(Nq, 1)), "pmk_query_fetch_grad")
+        G = Array{Float64,3}(undef, D, R, total[]); plane = Vector{Int32}(undef, total[])
+        check(ccall((:pmk_query_get_items_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int32}), q[], G, D * R, plane),
+              "pmk_query_get_items_grad")
+        return Yq, dYq, G, Int.(plane) .+ 1
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
 end
 
 """selectcandidates(scores) -> winners: per column (patch) of the G x P score matrix the row of the highest score; ties

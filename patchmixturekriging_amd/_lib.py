@@ -169,6 +169,13 @@ SIGNATURES = {
     "pmk_model_set_diag_global": (C.c_int, [_vp, C.c_void_p]),
     "pmk_query_fetch_dev": (C.c_int, [_vp, C.c_void_p, C.c_void_p]),
     "pmk_query_fetch_multi_dev": (C.c_int, [_vp, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pmk_query_items_grad": (C.c_int, [_vp, _kp]),
+    "pmk_query_mix_grad": (C.c_int, [_vp, _kp, C.c_int64, C.c_int64]),
+    "pmk_query_fetch_grad": (C.c_int, [_vp, _dp, C.c_int64]),
+    "pmk_query_fetch_grad_dev": (C.c_int, [_vp, C.c_void_p, C.c_int64]),
+    "pmk_query_get_items_grad": (C.c_int, [_vp, _dp, C.c_int64, _i32p]),
+    "pmk_predict_mixture_grad_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp,
+                                                  C.c_int64]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

@@ -1252,7 +1252,7 @@ void pmk_query_destroy(pmk_query *q)
     if (q->d_sort_scratch) (void)hipFree(q->d_sort_scratch);
     if (q->d_tasks) (void)hipFree(q->d_tasks);
     if (q->d_sync) (void)hipFree(q->d_sync);
-    dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre);
+    dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre); dev_free(q->d_gm); dev_free(q->d_dyq);
     dev_free(q->d_loo_x);               // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
@@ -1277,13 +1277,14 @@ int query_reserve(pmk_query *q, int64_t Nq)
     const bool regrow = q->nq_cap > 0;
     dev_free(q->d_xq);
     q->d_home = nullptr; q->d_cnt = nullptr; q->d_qoff = nullptr; q->d_yq = nullptr; q->d_vq = nullptr;
-    q->d_stage_r = nullptr; q->d_stage_t = nullptr;
+    q->d_stage_r = nullptr; q->d_stage_t = nullptr; q->d_stage_p = nullptr;
     q->nq_cap = 0;
     const size_t cap = (size_t)(Nq + (regrow ? Nq / 8 : 0)), c1 = std::max<size_t>(cap, 1);
     ArenaLayout a;
     const size_t o_xq = a.add(sizeof(double) * c1 * (size_t)m->D), o_st = a.add(sizeof(double) * 4 * c1),      // PLAN_STAGE rows
                  o_yq = a.add(sizeof(double) * c1), o_vq = a.add(sizeof(double) * c1), o_qoff = a.add(sizeof(int64_t) * (c1 + 1)),
-                 o_home = a.add(sizeof(int32_t) * c1), o_cnt = a.add(sizeof(int32_t) * (c1 + 1)), o_sr = a.add(sizeof(int32_t) * 4 * c1);
+                 o_home = a.add(sizeof(int32_t) * c1), o_cnt = a.add(sizeof(int32_t) * (c1 + 1)), o_sr = a.add(sizeof(int32_t) * 4 * c1),
+                 o_sp = a.add(sizeof(int32_t) * 4 * c1);
     char *base = nullptr;
     PMK_HIP(hipMalloc((void **)&base, a.bytes));
     q->d_xq = reinterpret_cast<double *>(base + o_xq);                 // o_xq == 0
@@ -1294,6 +1295,7 @@ int query_reserve(pmk_query *q, int64_t Nq)
     q->d_home = reinterpret_cast<int32_t *>(base + o_home);
     q->d_cnt = reinterpret_cast<int32_t *>(base + o_cnt);
     q->d_stage_r = reinterpret_cast<int32_t *>(base + o_sr);
+    q->d_stage_p = reinterpret_cast<int32_t *>(base + o_sp);
     q->nq_cap = (int64_t)cap;
     return 0;
 }
@@ -1314,6 +1316,7 @@ int query_set_items(pmk_query *q, int64_t n, const double *xq, const int32_t *re
     q->planned = false;
     q->R_items = 0;
     q->mixed_multi = false;
+    q->items_fn = q->grad_items = q->mixed_grad = false;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     q->ntasks = 0;
     if (n > 0) {
@@ -1323,6 +1326,7 @@ int query_set_items(pmk_query *q, int64_t n, const double *xq, const int32_t *re
         hipError_t e = hipMemcpyAsync(q->d_xq, xq, sizeof(double) * (size_t)(n * m->D), hipMemcpyDefault, s);
         if (e == hipSuccess) e = hipMemcpyAsync(q->d_item_region, region, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, s);
         if (e == hipSuccess) e = hipMemsetAsync(q->d_flag, 0, sizeof(int), s);
+        if (e == hipSuccess) e = hipMemsetAsync(q->d_item_plane, 0xff, sizeof(int32_t) * (size_t)n, s);   // -1: no plane
         if (e == hipSuccess) rc = launch_explicit_items(q, q->d_flag, s);
         if (e == hipSuccess && !rc) rc = launch_sort_items(q, s);
         if (e == hipSuccess && !rc) e = hipMemcpyAsync(&bad, q->d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -1348,13 +1352,14 @@ int grow_item_buffers(pmk_query *q, int64_t total)
     if (total <= q->item_cap) return 0;
     dev_free(q->d_item_t);
     q->d_item_region = nullptr; q->d_item_query = nullptr; q->d_sorted_item = nullptr; q->d_item_pos = nullptr;
+    q->d_item_plane = nullptr;
     q->d_u = nullptr; q->d_v = nullptr; q->d_w = nullptr;
     q->item_cap = 0;
     const size_t cap = (size_t)(total + total / 8 + 1024);
     ArenaLayout a;
     const size_t o_t = a.add(sizeof(double) * cap), o_u = a.add(sizeof(double) * cap), o_v = a.add(sizeof(double) * cap),
                  o_w = a.add(sizeof(double) * cap), o_r = a.add(sizeof(int32_t) * cap), o_q = a.add(sizeof(int32_t) * cap),
-                 o_s = a.add(sizeof(int32_t) * cap), o_p = a.add(sizeof(int32_t) * cap);
+                 o_s = a.add(sizeof(int32_t) * cap), o_p = a.add(sizeof(int32_t) * cap), o_pl = a.add(sizeof(int32_t) * cap);
     char *base = nullptr;
     PMK_HIP(hipMalloc((void **)&base, a.bytes));
     q->d_item_t = reinterpret_cast<double *>(base + o_t);              // o_t == 0
@@ -1365,6 +1370,7 @@ int grow_item_buffers(pmk_query *q, int64_t total)
     q->d_item_query = reinterpret_cast<int32_t *>(base + o_q);
     q->d_sorted_item = reinterpret_cast<int32_t *>(base + o_s);
     q->d_item_pos = reinterpret_cast<int32_t *>(base + o_p);
+    q->d_item_plane = reinterpret_cast<int32_t *>(base + o_pl);
     q->item_cap = (int64_t)cap;
     return 0;
 }
@@ -1450,6 +1456,7 @@ int pmk_query_plan(pmk_query *q, double radius, double delta)
     q->planned = false;
     q->R_items = 0;
     q->mixed_multi = false;
+    q->items_fn = q->grad_items = q->mixed_grad = false;
     q->total = 0;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     if (q->Nq > 0) {
@@ -1938,6 +1945,7 @@ static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_
     const int R = m->R_multi, qt = m->trend_q;      // with a trend the items kernel also emits kq . C_H: R + q columns
     q->R_items = 0;
     q->mixed_multi = false;
+    q->items_fn = q->grad_items = q->mixed_grad = false;
     // chunks of 16 items per region (item_means_kernel): prefix over the regions
     q->mcpre.assign((size_t)m->P + 1, 0);
     for (int64_t r = 0; r < m->P; ++r)
@@ -1972,6 +1980,7 @@ static int items_multi_common(pmk_query *q, const pmk_kernel_desc *th, int want_
     }
     if (rc) { q->R_items = 0; return rc; }
     q->var_items = want_var != 0;
+    q->items_fn = true;
     return 0;
 }
 
@@ -2125,6 +2134,7 @@ int pmk_query_items_loo_multi(pmk_query *q, int noisy, int want_var, int64_t *n_
     want_var = want_var != 0;
     q->R_items = 0;
     q->mixed_multi = false;
+    q->items_fn = q->grad_items = q->mixed_grad = false;
     if (q->um_cap < q->total * (R + qt)) {
         PMK_HIP(hipStreamSynchronize(s));       // earlier launches may still read the buffer replaced below
         dev_free(q->d_um);
@@ -2223,6 +2233,187 @@ int pmk_query_get_items_multi(pmk_query *q, double *U, int64_t ldu, double *v)
         for (size_t i = 0; i < T; ++i) v[i] = tmp[(size_t)pos[i]];
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ gradient of the blended mean
+static const char *family_name(int family)
+{
+    switch (family) {
+    case PMK_SPLINE34: return "PMK_SPLINE34";
+    case PMK_SPLINE12: return "PMK_SPLINE12";
+    case PMK_SPLINE32: return "PMK_SPLINE32";
+    case PMK_GAUSSIAN: return "PMK_GAUSSIAN";
+    case PMK_RQ: return "PMK_RQ";
+    case PMK_TRQ: return "PMK_TRQ";
+    case PMK_MODSQEXP: return "PMK_MODSQEXP";
+    case PMK_BB10: return "PMK_BB10";
+    case PMK_BB20: return "PMK_BB20";
+    case PMK_BB1EPS: return "PMK_BB1EPS";
+    case PMK_BB2EPS: return "PMK_BB2EPS";
+    default: return "unknown";
+    }
+}
+
+// a kernel whose profile has a psi = phi' / tau (pmk_device.h): stationary, and ModSqExp only at D = 1
+static int grad_kernel_ok(const pmk_kernel_desc *th, int D, const char *who, const char *role)
+{
+    if (!kernel_ok(th)) { set_error("%s: unknown kernel family (%s)", who, role); return -2; }
+    if (th->family >= PMK_BB10) {
+        set_error("%s: %s is a Brownian-bridge family (%s, %d): not differentiable on the diagonal, no gradient", who, role,
+                  family_name(th->family), th->family);
+        return -2;
+    }
+    if (th->family == PMK_MODSQEXP && D > 1) {
+        set_error("%s: %s is PMK_MODSQEXP, which is defined for D = 1 only (D = %d)", who, role, D);
+        return -2;
+    }
+    return 0;
+}
+
+int pmk_query_items_grad(pmk_query *q, const pmk_kernel_desc *th)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_grad: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_query_items_grad: the model holds %lld of %lld leaves; the gradient needs a model that holds every "
+                  "leaf", (long long)m->P, (long long)m->P_global);
+        return -4;
+    }
+    if (!m->multi_solved) {
+        set_error("pmk_query_items_grad: pmk_model_solve_multi has not run on the resident factor");
+        return -3;
+    }
+    if (q->R_items < 1 || !q->items_fn) {
+        set_error("pmk_query_items_grad: the last items on this plan must be those of pmk_query_items_multi or "
+                  "_multi_fitted (a member item of pmk_query_items_loo_multi is a lookup, not a function of x)");
+        return -2;
+    }
+    if (th) {
+        if (int rc = grad_kernel_ok(th, m->D, "pmk_query_items_grad", "theta")) return rc;
+    } else {
+        if (m->ths.empty()) { set_error("pmk_query_items_grad: the model holds no kernels (pmk_model_set_kernels)"); return -3; }
+        for (size_t r = 0; r < m->ths.size(); ++r)
+            if (int rc = grad_kernel_ok(&m->ths[r], m->D, "pmk_query_items_grad", "the model's own theta")) return rc;
+        th = fitted_theta(m);
+    }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    q->grad_items = q->mixed_grad = false;
+    const int64_t need = q->total * m->D * q->R_items;
+    if (q->gm_cap < need) {
+        PMK_HIP(hipStreamSynchronize(s));       // earlier launches may still read the buffer replaced below
+        dev_free(q->d_gm);
+        q->gm_cap = 0;
+        if (dev_alloc(&q->d_gm, need)) return -100;
+        q->gm_cap = need;
+    }
+    c->tic("items_grad");
+    const int rc = PMK_BY_DTYPE(m, launch_items_grad(q, th, s));
+    c->toc("items_grad");
+    if (rc) return rc;
+    q->grad_items = true;
+    return 0;
+}
+
+int pmk_query_mix_grad(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1)
+{
+    if (!q || !q->planned) { set_error("pmk_query_mix_grad: query is not planned"); return -1; }
+    if (!q->grad_items || q->R_items < 1) { set_error("pmk_query_mix_grad: pmk_query_items_grad has not run on this plan"); return -2; }
+    if (int rc = grad_kernel_ok(weight_th, 1, "pmk_query_mix_grad", "the blending profile")) return rc;
+    if (q0 < 0 || q1 > q->Nq || q0 > q1) { set_error("pmk_query_mix_grad: bad query range"); return -3; }
+    pmk_model *m = q->m;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    const int64_t need = q->Nq * m->D * q->R_items;
+    if (q->dyq_cap < need) {
+        PMK_HIP(hipStreamSynchronize(c->stream));
+        dev_free(q->d_dyq);
+        q->dyq_cap = 0;
+        if (dev_alloc(&q->d_dyq, need)) return -100;
+        q->dyq_cap = need;
+    }
+    c->tic("mix_grad");
+    const int rc = launch_mix_grad(q, *weight_th, q0, q1, c->stream);
+    c->toc("mix_grad");
+    if (rc) return rc;
+    q->mixed_grad = true;
+    return 0;
+}
+
+static int fetch_grad_common(pmk_query *q, double *dYq, int64_t lddy, hipMemcpyKind kind, const char *who)
+{
+    if (!q) { set_error("%s: query is NULL", who); return -1; }
+    if (!q->mixed_grad || !q->grad_items) { set_error("%s: pmk_query_mix_grad has not run", who); return -2; }
+    if (!dYq) { set_error("%s: dYq is NULL", who); return -2; }
+    if (lddy < q->Nq) { set_error("%s: lddy = %lld < Nq = %lld", who, (long long)lddy, (long long)q->Nq); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0)
+        PMK_HIP(hipMemcpy2DAsync(dYq, sizeof(double) * (size_t)lddy, q->d_dyq, sizeof(double) * (size_t)q->Nq,
+                                 sizeof(double) * (size_t)q->Nq, (size_t)(q->m->D * q->R_items), kind, c->stream));
+    return 0;
+}
+
+int pmk_query_fetch_grad(pmk_query *q, double *dYq, int64_t lddy)
+{
+    if (int rc = fetch_grad_common(q, dYq, lddy, hipMemcpyDeviceToHost, "pmk_query_fetch_grad")) return rc;
+    PMK_HIP(hipStreamSynchronize(q->m->ctx->stream));
+    return 0;
+}
+
+int pmk_query_fetch_grad_dev(pmk_query *q, double *dYq_dev, int64_t lddy)
+{
+    return fetch_grad_common(q, dYq_dev, lddy, hipMemcpyDeviceToDevice, "pmk_query_fetch_grad_dev");
+}
+
+int pmk_query_get_items_grad(pmk_query *q, double *G, int64_t ldg, int32_t *plane)
+{
+    if (!q || !q->planned) { set_error("pmk_query_get_items_grad: query is not planned"); return -1; }
+    if (G && !q->grad_items) { set_error("pmk_query_get_items_grad: pmk_query_items_grad has not run on this plan"); return -2; }
+    const size_t T = (size_t)q->total, DR = G ? (size_t)(q->m->D * q->R_items) : 0;
+    if (G && ldg < (int64_t)DR) { set_error("pmk_query_get_items_grad: ldg = %lld < D R = %lld", (long long)ldg, (long long)DR); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    if (T == 0) return 0;
+    if (plane) PMK_HIP(hipMemcpy(plane, q->d_item_plane, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
+    if (G) {
+        std::vector<int32_t> pos(T);
+        std::vector<double> tmp(T * DR);
+        PMK_HIP(hipMemcpy(pos.data(), q->d_item_pos, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
+        PMK_HIP(hipMemcpy(tmp.data(), q->d_gm, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < T; ++i)
+            for (size_t j = 0; j < DR; ++j) G[i * (size_t)ldg + j] = tmp[(size_t)pos[i] * DR + j];
+    }
+    return 0;
+}
+
+int pmk_predict_mixture_grad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                    double radius, double delta, double *Yq, int64_t ldyq, double *dYq, int64_t lddy)
+{
+    if (!m) { set_error("pmk_predict_mixture_grad_fitted: model is NULL"); return -1; }
+    if (m->P_global != m->P || m->leaf_base != 0) {
+        set_error("pmk_predict_mixture_grad_fitted: the model holds %lld of %lld leaves; the gradient needs a model that "
+                  "holds every leaf", (long long)m->P, (long long)m->P_global);
+        return -4;
+    }
+    if ((Yq && ldyq < Nq) || (dYq && lddy < Nq)) {
+        set_error("pmk_predict_mixture_grad_fitted: ldyq = %lld or lddy = %lld < Nq = %lld", (long long)ldyq, (long long)lddy,
+                  (long long)Nq);
+        return -4;
+    }
+    pmk_query *q = nullptr;
+    int rc = pmk_query_create(m, Nq, Xq, &q);
+    if (rc) return rc;
+    if (!(rc = pmk_query_plan(q, radius, delta)) && !(rc = pmk_query_items_multi_fitted(q, 0)) &&
+        !(rc = pmk_query_items_grad(q, nullptr)) && !(rc = pmk_query_mix_multi(q, weight_th, 0, Nq)) &&
+        !(rc = pmk_query_mix_grad(q, weight_th, 0, Nq))) {
+        if (Yq) rc = pmk_query_fetch_multi(q, Yq, ldyq, nullptr);
+        if (!rc && dYq) rc = pmk_query_fetch_grad(q, dYq, lddy);
+    }
+    pmk_query_destroy(q);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------ model selection

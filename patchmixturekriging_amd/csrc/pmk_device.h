@@ -231,6 +231,49 @@ __device__ __forceinline__ double dot_seq(const double *u, const double *x, int 
 
 #pragma clang fp contract(fast)
 
+// psi(tau) = phi'(tau) / tau of a stationary profile: grad_x k(x, z) = psi(|x - z|) (x - z), finite at tau = 0, so the
+// gradient kernels (pmk_grad.hip) never divide by a distance.  With r = a tau, t = max(1 - r, 0), a = p0:
+//   Spline34  -(56/3) a^2 (5 r + 1) t^5      Spline12  -12 a^2 t^2      Spline32  -20 a^2 t^3
+//   Gaussian  -2 p0 exp(-p0 tau^2)           RQ  -3 p0^(3/2) / (p0 + tau^2)^(5/2)      TRQ  p1 times RQ
+//   ModSqExp  exp(-p0 tau^2) (-2 p0 cos(p1 tau) - p1^2 sinc(p1 tau)),  sinc(0) = 1
+// A compact-support family returns (plus or minus) exactly 0 outside its support.  There is no reference to be
+// bit-equal with: no contract on the operation order, contraction allowed.  The Brownian-bridge families are not
+// differentiable on the diagonal and have no psi (NaN; the entry points refuse them).
+template <int FAM = 0, typename R = double>
+__device__ __forceinline__ R profile_dpsi(const pmk_kernel_desc &th, R tau)
+{
+    const R p0 = (R)th.p[0], p1 = (R)th.p[1];
+    switch (FAM ? FAM : th.family) {
+    case PMK_SPLINE34: {
+        const R r = tau * p0, t = fmax((R)1 - r, (R)0), t2 = t * t;
+        return ((R)(-56.0 / 3.0) * (p0 * p0)) * (((R)5 * r + (R)1) * ((t2 * t2) * t));
+    }
+    case PMK_SPLINE12: {
+        const R t = fmax((R)1 - tau * p0, (R)0);
+        return ((R)-12 * (p0 * p0)) * (t * t);
+    }
+    case PMK_SPLINE32: {
+        const R t = fmax((R)1 - tau * p0, (R)0);
+        return ((R)-20 * (p0 * p0)) * ((t * t) * t);
+    }
+    case PMK_GAUSSIAN:
+        return ((R)-2 * p0) * exp((-p0) * (tau * tau));
+    case PMK_RQ:
+    case PMK_TRQ: {
+        const R s2 = p0 + tau * tau, s = sqrt(s2), sa = sqrt(p0);
+        const R v = ((R)-3 * (sa * sa * sa)) / ((s2 * s2) * s);
+        return (FAM ? FAM : th.family) == PMK_TRQ ? p1 * v : v;
+    }
+    case PMK_MODSQEXP: {
+        const R x = p1 * tau;
+        const R sinc = x == (R)0 ? (R)1 : sin(x) / x;
+        return exp((-p0) * (tau * tau)) * (((R)-2 * p0) * cos(x) - (p1 * p1) * sinc);
+    }
+    default:
+        return (R)__builtin_nan("");
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // fp64 MFMA tile algebra.
 //

@@ -187,6 +187,7 @@ struct pmk_query {
     int32_t *d_cnt = nullptr;       // Nq : items per query (neighbours + 1)
     int32_t *d_stage_r = nullptr;   // PLAN_STAGE x nq_cap : first neighbour hits of the count pass (region), see plan_kernel
     double *d_stage_t = nullptr;    //                        ... and their t
+    int32_t *d_stage_p = nullptr;   //                        ... and their hyperplane (pre-order index)
     int64_t *d_qoff = nullptr;      // Nq+1
     int64_t total = 0;
     int64_t item_cap = 0;           // capacity of the per-item buffers (reused across plans)
@@ -195,6 +196,7 @@ struct pmk_query {
     int32_t *d_item_query = nullptr;    // total
     int32_t *d_sorted_item = nullptr;   // total: sorted position -> item
     int32_t *d_item_pos = nullptr;      // total: item -> sorted position
+    int32_t *d_item_plane = nullptr;    // total: pre-order hyperplane of a neighbour item (index into hp_v), -1 for home
     int64_t *d_roff = nullptr;          // P_global+1 (of the tree attached when the query was created: roff_P)
     int64_t roff_P = 0;
     std::vector<int64_t> roff;          // host copy
@@ -214,6 +216,12 @@ struct pmk_query {
     double *d_yqm = nullptr; int64_t yqm_cap = 0;     // Nq x R column-major
     int64_t *d_mcpre = nullptr; int64_t mcpre_cap = 0, mchunks = 0;   // chunks of 16 items per region: prefix [P+1]
     std::vector<int64_t> mcpre;         // host copy (source of the upload)
+    // gradient of the blended mean (pmk_grad.hip).  items_fn: the current U are functions of x (items_multi / _fitted,
+    // not the lookups of items_loo_multi); grad_items: pmk_query_items_grad has run on them; a new plan or new items
+    // discard both
+    bool items_fn = false, grad_items = false, mixed_grad = false;
+    double *d_gm = nullptr; int64_t gm_cap = 0;       // sorted items x (D x R_items): G[p][d + D c]
+    double *d_dyq = nullptr; int64_t dyq_cap = 0;     // Nq x (D x R_items) column-major: dYq[j + Nq (d + D c)]
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -261,6 +269,7 @@ inline const double *patch_sigma2s(const pmk_model *m) { return m->hyper_uniform
     int launch_loo_scatter(pmk_query *q, int noisy, const int32_t *d_mark, const int64_t *d_off, const double *d_ru, \
                            const double *d_rv, hipStream_t s);                                                       \
     int launch_loo_member_multi(pmk_query *q, int noisy, int want_var, int32_t *d_mark, hipStream_t s);              \
+    int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                   \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -281,6 +290,7 @@ int launch_sort_items(pmk_query *q, hipStream_t s);
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s);
+int launch_mix_grad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
                              const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);

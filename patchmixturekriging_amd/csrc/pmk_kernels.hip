@@ -112,10 +112,12 @@ __device__ __forceinline__ int find_leaf(const double *__restrict__ hv, const do
 // workgroup when it fits (P <= PLAN_LDS_NODES + 1): the hyperplane loop then reads LDS broadcasts instead
 // of issuing a dependent global load per hyperplane and per tree level.
 constexpr int PLAN_LDS_NODES = 2047;
-// The count pass keeps the first PLAN_STAGE neighbour hits of every query (region, t) in a staging array; the fill pass
-// copies them instead of walking the hyperplanes a second time (a workgroup in which some query has more hits than
+// The count pass keeps the first PLAN_STAGE neighbour hits of every query (region, t, plane) in a staging array; the fill
+// pass copies them instead of walking the hyperplanes a second time (a workgroup in which some query has more hits than
 // that walks again: same values either way).  Config C: 0.44 neighbours per query on average, the fill pass drops from
 // 1.18 ms to a copy.
+// item_plane: the pre-order index of the hyperplane a neighbour item was accepted at (the index into hp_v / hp_c of
+// pmk_bsp_arrays), -1 for the home item: the normal that the gradient of the item's weight needs (pmk_grad.hip).
 constexpr int PLAN_STAGE = 4;
 
 template <int D, bool FILL, bool LDS>
@@ -126,7 +128,8 @@ __global__ __launch_bounds__(256) void plan_kernel(int64_t Nq, const double *__r
                                                    int32_t *__restrict__ cnt_out, const int64_t *__restrict__ qoff,
                                                    int32_t *__restrict__ item_region, double *__restrict__ item_t,
                                                    int32_t *__restrict__ item_query, int32_t *__restrict__ stage_r,
-                                                   double *__restrict__ stage_t, int64_t stage_ld)
+                                                   double *__restrict__ stage_t, int64_t stage_ld,
+                                                   int32_t *__restrict__ item_plane, int32_t *__restrict__ stage_p)
 {
     extern __shared__ double plan_sm[];
     const double *hv = hv_g, *hc = hc_g;
@@ -140,10 +143,12 @@ __global__ __launch_bounds__(256) void plan_kernel(int64_t Nq, const double *__r
             for (int e = 0; e < cn; ++e) {
                 item_region[b0 + e] = stage_r[e * stage_ld + jq];
                 item_t[b0 + e] = stage_t[e * stage_ld + jq];
+                item_plane[b0 + e] = stage_p[e * stage_ld + jq];
                 item_query[b0 + e] = (int32_t)jq;
             }
             item_region[b0 + cn] = home_out[jq];
             item_t[b0 + cn] = 0.0;
+            item_plane[b0 + cn] = -1;
             item_query[b0 + cn] = (int32_t)jq;
             return;
         }
@@ -273,10 +278,12 @@ __global__ __launch_bounds__(256) void plan_kernel(int64_t Nq, const double *__r
                 if (FILL) {
                     item_region[base + count] = reg;
                     item_t[base + count] = tt;
+                    item_plane[base + count] = c0 + 32 * w + bpos;
                     item_query[base + count] = (int32_t)j;
                 } else if (count < PLAN_STAGE) {
                     stage_r[count * stage_ld + j] = reg;
                     stage_t[count * stage_ld + j] = tt;
+                    stage_p[count * stage_ld + j] = c0 + 32 * w + bpos;
                 }
                 ++count;
             }
@@ -287,6 +294,7 @@ __global__ __launch_bounds__(256) void plan_kernel(int64_t Nq, const double *__r
     if (FILL) {
         item_region[base + count] = home;     // home region last (mixtureGP.jl:237-239)
         item_t[base + count] = 0.0;
+        item_plane[base + count] = -1;
         item_query[base + count] = (int32_t)j;
     } else {
         home_out[j] = home;
@@ -308,7 +316,8 @@ static int launch_plan_D(pmk_query *q, double radius, double delta, bool fill, h
 #define PMK_PLAN(FILL_, LDS_)                                                                                          \
     hipLaunchKernelGGL((plan_kernel<D, FILL_, LDS_>), grid, dim3(256), bytes, s, q->Nq, q->d_xq, m->d_hv, m->d_hc,      \
                        m->d_pre, m->levels, m->dot_mode, m->P_global, radius, delta, q->d_home, q->d_cnt, q->d_qoff,                \
-                       q->d_item_region, q->d_item_t, q->d_item_query, q->d_stage_r, q->d_stage_t, q->nq_cap)
+                       q->d_item_region, q->d_item_t, q->d_item_query, q->d_stage_r, q->d_stage_t, q->nq_cap,   \
+                       q->d_item_plane, q->d_stage_p)
     if (fill) { if (lds) PMK_PLAN(true, true); else PMK_PLAN(true, false); }
     else      { if (lds) PMK_PLAN(false, true); else PMK_PLAN(false, false); }
 #undef PMK_PLAN

@@ -37,6 +37,7 @@ static int no_gpu(const char *what)
     int launch_loo_compact(pmk_query *, const int32_t *, const int64_t *, double *, int32_t *, double *, hipStream_t) { return no_gpu("launch_loo_compact"); } \
     int launch_loo_scatter(pmk_query *, int, const int32_t *, const int64_t *, const double *, const double *, hipStream_t) { return no_gpu("launch_loo_scatter"); } \
     int launch_loo_member_multi(pmk_query *, int, int, int32_t *, hipStream_t) { return no_gpu("launch_loo_member_multi"); } \
+    int launch_items_grad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_grad"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -51,6 +52,7 @@ int launch_sort_items(pmk_query *, hipStream_t) { return no_gpu("launch_sort_ite
 int launch_mix(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix"); }
 int launch_mix_multi(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_multi"); }
 int launch_trend_items(pmk_query *, int, int, bool, hipStream_t) { return no_gpu("launch_trend_items"); }
+int launch_mix_grad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_grad"); }
 int launch_loo_scatter_multi(pmk_query *, const pmk_query *, int, int, const int32_t *, const int64_t *, hipStream_t)
 {
     return no_gpu("launch_loo_scatter_multi");

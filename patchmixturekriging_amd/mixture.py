@@ -542,6 +542,7 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_counts(self.h, C.byref(t), C.byref(f), C.byref(o)))
         self.total, self.first_owned, self.num_owned = t.value, f.value, o.value
         self.R_items = 0                    # a new plan discards the items, as in the library
+        self.grad_items = False
         return self.total
 
     def region_offsets(self, P_global):
@@ -602,6 +603,7 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_items_loo_multi(self.h, int(bool(noisy)), int(bool(variance)), C.byref(nm), C.byref(no)),
                    "pmk_query_items_loo_multi")
         self.variance, self.R_items = bool(variance), int(m.R)
+        self.grad_items = False
         return nm.value, no.value
 
     def item_values_multi(self):
@@ -623,6 +625,7 @@ class DeviceQuery:
             raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
         _lib.check(self.L.pmk_query_items_multi_fitted(self.h, int(bool(variance))), "pmk_query_items_multi_fitted")
         self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
+        self.grad_items = False
 
     def item_buffers(self):
         u, v = C.c_void_p(), C.c_void_p()
@@ -691,6 +694,7 @@ class DeviceQuery:
         d = theta.desc()
         _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
         self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
+        self.grad_items = False
 
     def mix_multi(self, weight_theta, q0=0, q1=None):
         d = weight_theta.desc()
@@ -705,6 +709,57 @@ class DeviceQuery:
                    "pmk_query_fetch_multi")
         return Yq, Vq
 
+    # ---- gradient of the blended mean (pmk_grad.hip)
+    def items_grad(self, theta=None):
+        """pmk_query_items_grad: the gradient of every item mean of the last items_multi / items_multi_fitted on this plan,
+        with `theta` for every patch or (None) the model's own kernels.  Closure-carrying kernels raise TypeError and
+        Brownian-bridge kernels ValueError before any device call."""
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            d = _grad_kernel(theta, "items_grad")
+            ptr = C.byref(d)
+        _lib.check(self.L.pmk_query_items_grad(self.h, ptr), "pmk_query_items_grad")
+        self.grad_items = True
+
+    def mix_grad(self, weight_theta, q0=0, q1=None):
+        """pmk_query_mix_grad: the gradient of the blend of mix_multi for queries [q0, q1), the item list held fixed"""
+        d = _grad_kernel(weight_theta, "mix_grad")
+        _lib.check(self.L.pmk_query_mix_grad(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
+                   "pmk_query_mix_grad")
+
+    def fetch_grad(self):
+        """dYq [Nq, R, D]: dYq[j, c, d] = dY_c/dx_d at query j"""
+        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
+        if R < 1:
+            raise _lib.PmkError("fetch_grad: no items_multi or items_multi_fitted has run")
+        buf = np.empty((R, D, max(self.Nq, 1)))                 # dYq[j + lddy (d + D c)]
+        _lib.check(self.L.pmk_query_fetch_grad(self.h, _d(buf), max(self.Nq, 1)), "pmk_query_fetch_grad")
+        return np.ascontiguousarray(buf[:, :, :self.Nq].transpose(2, 0, 1))
+
+    def fetch_grad_into(self, dYq):
+        """pmk_query_fetch_grad_dev: dYq is a device array of shape (R, D, Nq), C-contiguous (element [c, d, j] is
+        dY_c/dx_d at query j): device-to-device on the context's stream, no host synchronisation"""
+        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
+        ga = self._device_out(dYq, "dYq")
+        if ga.shape != (R, D, self.Nq) or (self.Nq > 0 and ga.strides != (D * self.Nq, self.Nq, 1)):
+            raise ValueError("dYq must be a C-contiguous device array of shape (%d, %d, %d), not %s" % (R, D, self.Nq, ga.shape))
+        _lib.check(self.L.pmk_query_fetch_grad_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_grad_dev")
+
+    def item_grads(self):
+        """pmk_query_get_items_grad -> (G [total, R, D], plane [total]) in the item order of debug(): G[i, c, d] is the
+        gradient of item i's mean of column c; plane[i] is the pre-order hyperplane (row of fetchhyperplanes' arrays) a
+        neighbour item was accepted at, -1 for a home item.  G is None before items_grad."""
+        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
+        T = max(int(self.total), 1)
+        plane = np.empty(T, dtype=np.int32)
+        G = np.empty((T, R, D)) if getattr(self, "grad_items", False) and R >= 1 else None
+        _lib.check(self.L.pmk_query_get_items_grad(self.h, None if G is None else _d(G), R * D,
+                                                   plane.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_query_get_items_grad")
+        return (None if G is None else G[:self.total]), plane[:self.total]
+
     def debug(self):
         home = np.empty(self.Nq, dtype=np.int64)
         off = np.empty(self.Nq + 1, dtype=np.int64)
@@ -715,6 +770,18 @@ class DeviceQuery:
         n = self.total
         return dict(home=home, item_offsets=off, item_region=reg[:n], item_t=t[:n], item_w=w[:n], item_u=u[:n],
                     item_v=v[:n])
+
+
+def _grad_kernel(theta, who):
+    """the descriptor of a kernel the gradient calls accept, checked before any device call: closure-carrying kernels are
+    refused with the TypeError of the trend, the Brownian-bridge families (not differentiable on the diagonal) with a
+    ValueError"""
+    _refuse_closure_kernel(theta, who)
+    d = theta.desc()
+    if d.family >= 10:                          # PMK_BB10 .. PMK_BB2EPS
+        raise ValueError("%s: %s is a Brownian-bridge kernel, which is not differentiable on the diagonal: no gradient"
+                         % (who, type(theta).__name__))
+    return d
 
 
 def kernel_points(theta, X):
@@ -1066,6 +1133,31 @@ def querymixtureGP_multi(Xq, eta, root, levels, radius, delta, theta, sigma2, we
     q.items_multi(theta, variance)
     q.mix_multi(weight_theta)
     return q.fetch_multi(model.R)
+
+
+def querymixtureGP_grad(Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta):
+    """querymixtureGP_multi's blended means and their gradient -> (Yq [Nq, R], dYq [Nq, R, D]), dYq[j, c, d] = dY_c/dx_d,
+    for the R columns of fitmixtureGP_multi_ or fitmixtureGP_trend_.  No triangular solve runs.  The derivative holds each
+    query's item list fixed: where the list changes (the radius cut-off unless the weight profile vanishes there, a delta
+    test, a change of home leaf) the blend itself jumps and has no derivative.  Closure-carrying kernels raise TypeError,
+    Brownian-bridge kernels ValueError, before any device call."""
+    _grad_kernel(theta, "querymixtureGP_grad")
+    _grad_kernel(weight_theta, "querymixtureGP_grad")
+    if eta._model is None or getattr(eta, "C_set", None) is None:
+        raise _lib.PmkError("fitmixtureGP_multi_ must run before querymixtureGP_grad")
+    Xq = np.asarray(Xq, dtype=np.float64)
+    if Xq.ndim == 1:
+        Xq = Xq[None, :]
+    Xq = as_points(Xq)
+    model = eta._model
+    model.set_bsp(root, 0)
+    q = DeviceQuery(model, Xq)
+    q.plan(radius, delta)
+    q.items_multi(theta, False)
+    q.items_grad(theta)
+    q.mix_multi(weight_theta)
+    q.mix_grad(weight_theta)
+    return q.fetch_multi(model.R)[0], q.fetch_grad()
 
 
 # ---- model selection: is this (theta, sigma2) any good on this patch?  The reference picks both by hand
