@@ -374,6 +374,42 @@ def _predict_fitted(b, Xq):
     return Y
 
 
+def _fd_ratio(b, trend, Xc, stencil, sigs, dY, h, oths, Xs, u=2.0 ** -53, check=True):
+    """the central-difference rule: fd_h = (f(x + h e_d) - f(x - h e_d)) / 2h of pmk_predict_mixture_multi_fitted against
+    dY [len(Xc), R, D], tolerance |fd_2h - fd_h| + 2 eps_f / h per component, asserted unless check is False ->
+    (worst err / tol, median over the queries of the largest tol / the largest |dY|).  b: .model, .wth, .radius, .delta,
+    .R; stencil(x): the points x +- h e_d, x +- 2h e_d per d; sigs: (home, neighbour regions) per query; oths, Xs: the
+    oracle kernel and the points of every patch; u: the unit roundoff of the model's items"""
+    D, R = Xc.shape[1], b.R
+    Yfd = _predict_fitted(b, np.vstack([p for x in Xc for p in stencil(x)])).reshape(len(Xc), D, 4, R)
+    # eps_f of one device prediction: the blend is a convex combination of items, each n products and sums
+    Cs = b.model.weights_multi()
+    betas = b.model.trend()[0] if trend else [None] * len(Cs)
+    worst, rel = 0.0, []
+    for k, x in enumerate(Xc):
+        home, reg = sigs[k]
+        mag = np.zeros(R)
+        for r in list(reg) + [home]:
+            a = np.abs(O.cross_kernel_matrix(oths[r], x[None, :], Xs[r])[0]) @ np.abs(Cs[r])
+            n = len(Xs[r])
+            if betas[r] is not None and len(betas[r]):
+                hb = np.concatenate([[1.0], x])[:len(betas[r])]
+                a, n = a + np.abs(hb) @ np.abs(betas[r]), n + len(hb)
+            mag = np.maximum(mag, (n + len(reg) + 9) * a)
+        eps_f = u * mag
+        tols = []
+        for d in range(D):
+            fp, fm, fp2, fm2 = Yfd[k, d]
+            fd_h, fd_2h = (fp - fm) / (2 * h), (fp2 - fm2) / (4 * h)
+            tol = np.abs(fd_2h - fd_h) + 2 * eps_f / h
+            err = np.abs(fd_h - dY[k, :, d])
+            worst = max(worst, float((err / tol).max()))
+            tols.append(float(tol.max()))
+            assert not check or np.all(err <= tol), (k, d, err, tol)
+        rel.append(max(tols) / max(float(np.abs(dY[k]).max()), 1e-300))
+    return worst, float(np.median(rel))
+
+
 @pytest.mark.parametrize("D,R,family,trend", [(2, 2, "spline34", None), (2, 2, "rq", "linear"), (3, 1, "gaussian", "constant")])
 def test_device_gradient_equals_central_differences_of_the_device_predictor(D, R, family, trend):
     b = Blend(D, R, family, trend)
@@ -394,30 +430,7 @@ def test_device_gradient_equals_central_differences_of_the_device_predictor(D, R
     assert len(pick) == 16 and len(with_nb) >= 2
     Xc = b.Xq[pick]
     q = b.staged(Xc)
-    dY = q.fetch_grad()
-    Yfd = _predict_fitted(b, np.vstack([p for x in Xc for p in stencil(x)])).reshape(16, D, 4, R)
-    # eps_f of one device prediction: the blend is a convex combination of items, each n products and sums
-    Cs = b.model.weights_multi()
-    betas = b.model.trend()[0] if trend else [None] * len(Cs)
-    worst = 0.0
-    for k, x in enumerate(Xc):
-        home, reg, _ = signature(x)
-        mag = np.zeros(R)
-        for r in list(reg) + [home]:
-            a = np.abs(O.cross_kernel_matrix(b.oth, x[None, :], b.Xs[r])[0]) @ np.abs(Cs[r])
-            n = len(b.Xs[r])
-            if betas[r] is not None and len(betas[r]):
-                hb = np.concatenate([[1.0], x])[:len(betas[r])]
-                a, n = a + np.abs(hb) @ np.abs(betas[r]), n + len(hb)
-            mag = np.maximum(mag, (n + len(reg) + 9) * a)
-        eps_f = 2.0 ** -53 * mag
-        for d in range(D):
-            fp, fm, fp2, fm2 = Yfd[k, d]
-            fd_h, fd_2h = (fp - fm) / (2 * h), (fp2 - fm2) / (4 * h)
-            tol = np.abs(fd_2h - fd_h) + 2 * eps_f / h
-            err = np.abs(fd_h - dY[k, :, d])
-            worst = max(worst, float((err / tol).max()))
-            assert np.all(err <= tol), (k, d, err, tol)
+    worst, _ = _fd_ratio(b, trend, Xc, stencil, [signature(x)[:2] for x in Xc], q.fetch_grad(), h, [b.oth] * len(b.Xs), b.Xs)
     _record(test="blend_fd", D=D, R=R, family=family, trend=trend, ratio=worst, with_neighbours=len([j for j in pick if j in with_nb]))
 
 
