@@ -560,21 +560,26 @@ class DeviceQuery:
             raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
         _lib.check(self.L.pmk_query_items_fitted(self.h), "pmk_query_items_fitted")
 
+    def _blend_loo_model(self, who):
+        """the model, if the blended leave-one-out can run on it with this query (the states the library refuses too)"""
+        m = self.model
+        if not getattr(m, "_from_tree", False):
+            raise _lib.PmkError("%s: the model was built from lists of patches, not by from_tree" % who)
+        if self.Nq != m.N:
+            raise _lib.PmkError("%s: the query has %d points, the model %d: query j must be training point j"
+                                % (who, self.Nq, m.N))
+        if not getattr(m, "_all_leaves", False):
+            raise _lib.PmkError("%s: the model holds a shard of the leaves; the blended leave-one-out needs all" % who)
+        if not getattr(m, "_has_kernels", False):
+            raise _lib.PmkError("the model holds no kernels: fit it first")
+        return m
+
     def items_loo(self, noisy=False):
         """pmk_query_items_loo: stage 2 of the blended leave-one-out, for a query whose points ARE the training points of a
         tree-built model (query j = global point j) -> (n_member, n_strip).  An item whose patch holds the point comes
         from the resident leave-one-out values (no strip); any other item is items_fitted's.  noisy: the variances include
         each patch's sigma2.  Follow with mix() and fetch() as after items()."""
-        m = self.model
-        if not getattr(m, "_from_tree", False):
-            raise _lib.PmkError("items_loo: the model was built from lists of patches, not by from_tree")
-        if self.Nq != m.N:
-            raise _lib.PmkError("items_loo: the query has %d points, the model %d: query j must be training point j"
-                                % (self.Nq, m.N))
-        if not getattr(m, "_all_leaves", False):
-            raise _lib.PmkError("items_loo: the model holds a shard of the leaves; the blended leave-one-out needs all")
-        if not getattr(m, "_has_kernels", False):
-            raise _lib.PmkError("the model holds no kernels: fit it first")
+        m = self._blend_loo_model("items_loo")
         m._need(loo=True)
         nm, ns = C.c_int64(), C.c_int64()
         _lib.check(self.L.pmk_query_items_loo(self.h, int(bool(noisy)), C.byref(nm), C.byref(ns)), "pmk_query_items_loo")
@@ -587,16 +592,7 @@ class DeviceQuery:
         With a trend of q basis functions a member item of a patch of n <= q points is NaN (means and variance): no
         leave-one-out prediction exists from fewer than q points; a non-member item of such a patch stays valid.
         variance=False: means only, no strip kernel runs.  Follow with mix_multi() and fetch_multi()."""
-        m = self.model
-        if not getattr(m, "_from_tree", False):
-            raise _lib.PmkError("items_loo_multi: the model was built from lists of patches, not by from_tree")
-        if self.Nq != m.N:
-            raise _lib.PmkError("items_loo_multi: the query has %d points, the model %d: query j must be training point j"
-                                % (self.Nq, m.N))
-        if not getattr(m, "_all_leaves", False):
-            raise _lib.PmkError("items_loo_multi: the model holds a shard of the leaves; the blended leave-one-out needs all")
-        if not getattr(m, "_has_kernels", False):
-            raise _lib.PmkError("the model holds no kernels: fit it first")
+        m = self._blend_loo_model("items_loo_multi")
         m._need(loo=True)           # the library's order: a new fit makes both stale and is told about loo() first
         m._need(multi=True)
         nm, no = C.c_int64(), C.c_int64()
