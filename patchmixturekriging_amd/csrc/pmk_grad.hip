@@ -20,6 +20,7 @@
 // its items, and through the blend in every query that uses one of them.  The q trend columns of C are not differentiated.
 #include "pmk_device.h"
 #include "pmk_dispatch.h"
+#include "pmk_items.h"
 #include "pmk_mfma.h"
 
 namespace pmk {
@@ -28,7 +29,7 @@ namespace PMK_NS {
 constexpr int IG_THREADS = 256;
 constexpr int IG_RP = PMK_MAX_OUTPUTS;
 
-// The chunking, XCD remap, binary search over cpre and operand layout of item_means_kernel: one wave per chunk of (up
+// The chunking (chunk_region, pmk_items.h), XCD remap and operand layout of item_means_kernel: one wave per chunk of (up
 // to) 16 items of one region.  Lane l evaluates tau once for (item l & 15, point k0 + (l >> 4)), forms the D operands
 // psi (q_d - x_d) and issues D MFMAs against the same row of C_r.  R: target columns emitted (c < R only).
 // beta: the model's trend coefficients when the trend is linear (beta[(r 16 + c) 5 + 1 + d]), else null.
@@ -48,13 +49,7 @@ __global__ __launch_bounds__(IG_THREADS) void item_grads_kernel(const PatchDesc 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t g = (int64_t)xcd_remap((int)blockIdx.x, (int)gridDim.x) * (IG_THREADS / 64) + wave;
     if (g >= nchunks) return;
-    int lo = 0, hi = P;                                      // cpre[lo] <= g < cpre[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (cpre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    const int r = lo;
+    const int r = chunk_region(cpre, P, g);
     const int64_t first = roff[r] + (g - cpre[r]) * 16;
     const int count = (int)min((int64_t)16, roff[r + 1] - first);
     const PatchDesc pd = descs[r];
@@ -63,14 +58,7 @@ __global__ __launch_bounds__(IG_THREADS) void item_grads_kernel(const PatchDesc 
     else th = th_arg;
     const int li = lane & 15, lg = lane >> 4;
     real q[D];
-    if (li < count) {
-        const int64_t qi = item_query[sorted_item[first + li]];
-#pragma unroll
-        for (int d = 0; d < D; ++d) q[d] = (real)xq[qi * D + d];
-    } else {
-#pragma unroll
-        for (int d = 0; d < D; ++d) q[d] = (real)0;
-    }
+    chunk_query_point(first, count, li, sorted_item, item_query, xq, q);
     const real *xs = x + pd.xoff;
     const real *Cb = Cm + pd.yoff * IG_RP + li;
     const int ld = pd.ld, n = pd.n;
@@ -105,8 +93,7 @@ __global__ __launch_bounds__(IG_THREADS) void item_grads_kernel(const PatchDesc 
         }
     }
     if (li >= R) return;
-    bool bad = info[r] != 0;
-    if (tinfo) bad = bad || tinfo[r] != 0;
+    const bool bad = patch_is_bad(info, tinfo, r);
     const double nan = __builtin_nan("");
     const double *b = beta ? beta + ((int64_t)r * TR_RP + li) * TQ_MAX + 1 : nullptr;
 #pragma unroll
@@ -148,7 +135,7 @@ int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
 
 #ifndef PMK_REAL_F32
 // One thread per query; the items in the order of mix_multi_kernel (neighbours in hyperplane order, home last with
-// w = 1, t = 0, no plane).  S is formed exactly as mix_multi_kernel forms it; then, per (c, d), the sum over the items of
+// w = 1, t = 0, no plane).  S is mix_multi_kernel's (blend_weight_sum); then, per (c, d), the sum over the items of
 // w_i G_{i,d,c} + (u_{i,c} - Y_c) dw_i/dx_d in item order (the home item adds its G alone), divided by S.  u_i - Y_c is
 // taken as sum_k w_k (u_i - u_k) / S and never as a difference against the rounded blend: where the patches agree
 // (u_i close to Y_c, both far from zero) that difference would carry the rounding of Y_c, not of u_i - Y_c.
@@ -163,11 +150,7 @@ __global__ __launch_bounds__(256) void mix_grad_kernel(int64_t q0, int64_t q1, i
     const int64_t j = q0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= q1) return;
     const int64_t b = qoff[j], e = qoff[j + 1];
-    double sw = 0.0;
-    for (int64_t it = b; it < e; ++it) {
-        const double w = (it == e - 1) ? 1.0 : profile(wth, fabs(item_t[it]));
-        sw = (it == b) ? w : sw + w;
-    }
+    const double sw = blend_weight_sum(wth, item_t, b, e);
     for (int col = 0; col < R; ++col) {
         double acc[MAX_D];
         for (int64_t it = b; it < e; ++it) {
@@ -182,7 +165,7 @@ __global__ __launch_bounds__(256) void mix_grad_kernel(int64_t q0, int64_t q1, i
             const double c = -(profile_dpsi(wth, fabs(t)) * t);          // dw_i/dx_d = c v_d
             double dev = 0.0;                                            // S (u_i - Y) = sum_k w_k (u_i - u_k), k in item order
             for (int64_t k = b; k < e; ++k) {
-                const double wk = (k == e - 1) ? 1.0 : profile(wth, fabs(item_t[k]));
+                const double wk = blend_weight(wth, item_t, k, e);
                 dev += wk * (ui - U[(int64_t)item_pos[k] * ldu + col]);
             }
             const double uy = dev / sw;
@@ -200,7 +183,7 @@ int launch_mix_grad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_
 {
     if (q1 <= q0) return 0;
     const pmk_model *m = q->m;
-    hipLaunchKernelGGL(mix_grad_kernel, dim3((unsigned)((q1 - q0 + 255) / 256)), dim3(256), 0, s, q0, q1, q->Nq, q->d_qoff,
+    hipLaunchKernelGGL(mix_grad_kernel, grid256(q1 - q0), dim3(256), 0, s, q0, q1, q->Nq, q->d_qoff,
                        q->d_item_t, q->d_item_pos, q->d_item_plane, q->d_um, q->um_ld, q->R_items, m->D, q->d_gm, m->d_hv,
                        m->d_pre, wth, q->d_dyq);
     PMK_HIP(hipGetLastError());

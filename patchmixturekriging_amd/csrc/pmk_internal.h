@@ -14,7 +14,7 @@ namespace pmk {
 constexpr int TILE = 128;       // factorisation tile edge; slabs are padded to a multiple of it
 constexpr int MAX_D = 4;        // input dimension limit (the reference's examples use 1, 2 and 3)
 constexpr int TQ = 256;         // query columns per prediction strip (8 waves x 32)
-// layout of the per-patch trend state and of the multi-output blocks, shared by pmk_trend.hip and pmk_loo_mix_multi.hip
+// layout of the per-patch trend state and of the multi-output blocks, shared by pmk_trend.hip and pmk_loo_mix.hip
 constexpr int TQ_MAX = 1 + MAX_D;             // basis functions of the linear trend at D = 4; leading dimension of L_G
 constexpr int TR_RP = PMK_MAX_OUTPUTS;        // columns of a row of the target / weight block
 
@@ -237,6 +237,9 @@ namespace pmk {
 
 // sigma2 of the resident factor per local patch: the device array after pmk_model_fit_patches, one value otherwise
 inline const double *patch_sigma2s(const pmk_model *m) { return m->hyper_uniform ? nullptr : m->d_sigma2s; }
+
+// grid of a kernel of 256 threads per workgroup with one thread per entry
+inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // ---- launchers implemented in the .hip files (all enqueue on `s`) ----
 // precision-generic kernels live in namespaces f64 / f32 (the same sources compiled twice)

@@ -2,6 +2,7 @@
 
 #include "pmk_device.h"
 #include "pmk_dispatch.h"
+#include "pmk_items.h"
 
 namespace pmk {
 
@@ -307,7 +308,7 @@ template <int D>
 static int launch_plan_D(pmk_query *q, double radius, double delta, bool fill, hipStream_t s)
 {
     const pmk_model *m = q->m;
-    dim3 grid((unsigned)((q->Nq + 255) / 256));
+    const dim3 grid = grid256(q->Nq);
     const int64_t nn = m->P_global - 1;
     const bool lds = nn <= PLAN_LDS_NODES;
     // the tree (when it fits) + the four waves' scratch (plan_kernel: WAVE_DOUBLES)
@@ -462,7 +463,7 @@ __global__ void iota_kernel(int32_t *v, int64_t n)
 int launch_iota(int32_t *d, int64_t n, hipStream_t s)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, n);
+    hipLaunchKernelGGL(iota_kernel, grid256(n), dim3(256), 0, s, d, n);
     PMK_HIP(hipGetLastError());
     return 0;
 }
@@ -619,7 +620,7 @@ int launch_sort_items(pmk_query *q, hipStream_t s)
                            bitems, nb, P, hist);
     } else {
         PMK_HIP(hipMemsetAsync(hist, 0, sizeof(int32_t) * (size_t)(P * nb), s));
-        hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q->d_item_region, n, bitems, nb, P, hist);
+        hipLaunchKernelGGL(sort_hist_kernel, grid256(n), dim3(256), 0, s, q->d_item_region, n, bitems, nb, P, hist);
     }
     hipLaunchKernelGGL(sort_scan_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, hist, nb, P, total);
     hipLaunchKernelGGL(sort_roff_kernel, dim3(1), dim3(256), 0, s, total, P, q->d_roff);
@@ -649,7 +650,7 @@ __global__ void export_requests_kernel(int64_t first, int64_t n, const int32_t *
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s)
 {
     if (n == 0) return 0;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const dim3 grid = grid256(n), block(256);
     const int rc = dispatch_dim(q->m->D, [&](auto dd) {
         hipLaunchKernelGGL(export_requests_kernel<dd()>, grid, block, 0, s, first, n, q->d_sorted_item, q->d_item_query,
                            q->d_item_region, q->d_xq, x_out, region_out);
@@ -674,7 +675,7 @@ __global__ void export_request_diag_kernel(int64_t first, int64_t n, const int32
 int launch_export_request_diag(pmk_query *q, int64_t first, int64_t n, double *diag_out, hipStream_t s)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(export_request_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, first, n,
+    hipLaunchKernelGGL(export_request_diag_kernel, grid256(n), dim3(256), 0, s, first, n,
                        q->d_sorted_item, q->d_item_query, q->d_qdiag, diag_out);
     PMK_HIP(hipGetLastError());
     return 0;
@@ -694,7 +695,7 @@ __global__ void export_results_kernel(int64_t n, const int32_t *__restrict__ ite
 int launch_export_results(pmk_query *q, double *u_out, double *v_out, hipStream_t s)
 {
     if (q->total == 0) return 0;
-    hipLaunchKernelGGL(export_results_kernel, dim3((unsigned)((q->total + 255) / 256)), dim3(256), 0, s, q->total,
+    hipLaunchKernelGGL(export_results_kernel, grid256(q->total), dim3(256), 0, s, q->total,
                        q->d_item_pos, q->d_u, q->d_v, u_out, v_out);
     PMK_HIP(hipGetLastError());
     return 0;
@@ -719,6 +720,7 @@ __global__ void explicit_items_kernel(int64_t n, const int32_t *__restrict__ reg
 int launch_explicit_items(pmk_query *q, int *d_bad, hipStream_t s)
 {
     const pmk_model *m = q->m;
+    // not grid256: Nq + 1 entries, thread Nq closes the offsets with qoff[Nq]
     hipLaunchKernelGGL(explicit_items_kernel, dim3((unsigned)((q->Nq + 256) / 256)), dim3(256), 0, s, q->Nq,
                        q->d_item_region, (int32_t)m->leaf_base, (int32_t)(m->leaf_base + m->P), q->d_item_query,
                        q->d_item_t, q->d_qoff, q->d_home, d_bad);
@@ -739,12 +741,7 @@ __global__ __launch_bounds__(256) void mix_kernel(int64_t q0, int64_t q1, const 
     const int64_t j = q0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= q1) return;
     const int64_t b = qoff[j], e = qoff[j + 1];
-    double sw = 0.0;
-    for (int64_t it = b; it < e; ++it) {
-        const double w = (it == e - 1) ? 1.0 : profile(wth, fabs(item_t[it]));
-        w_out[it] = w;
-        sw = (it == b) ? w : sw + w;
-    }
+    const double sw = blend_weight_sum(wth, item_t, b, e, [&](int64_t it, double w) { w_out[it] = w; });
     double y = 0.0, vv = 0.0;
     for (int64_t it = b; it < e; ++it) {
         const double w = w_out[it] / sw;
@@ -760,7 +757,7 @@ __global__ __launch_bounds__(256) void mix_kernel(int64_t q0, int64_t q1, const 
 int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s)
 {
     if (q1 <= q0) return 0;
-    hipLaunchKernelGGL(mix_kernel, dim3((unsigned)((q1 - q0 + 255) / 256)), dim3(256), 0, s, q0, q1, q->d_qoff,
+    hipLaunchKernelGGL(mix_kernel, grid256(q1 - q0), dim3(256), 0, s, q0, q1, q->d_qoff,
                        q->d_item_t, q->d_item_pos, q->d_u, q->d_v, wth, q->d_w, q->d_yq, q->d_vq);
     PMK_HIP(hipGetLastError());
     return 0;

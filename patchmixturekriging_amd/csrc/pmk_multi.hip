@@ -16,6 +16,7 @@
 // once, plus 2 x ld x 16 elements of Y / C per patch.  The items kernel reads only the points and C_r (L2-resident per
 // region); it is VALU bound on the kernel evaluations.
 #include "pmk_dispatch.h"
+#include "pmk_items.h"
 #include "pmk_mfma.h"
 
 namespace pmk {
@@ -194,13 +195,7 @@ __global__ __launch_bounds__(IM_THREADS) void item_means_kernel(const PatchDesc 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t g = (int64_t)xcd_remap((int)blockIdx.x, (int)gridDim.x) * (IM_THREADS / 64) + wave;
     if (g >= nchunks) return;
-    int lo = 0, hi = P;                                      // cpre[lo] <= g < cpre[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (cpre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    const int r = lo;
+    const int r = chunk_region(cpre, P, g);
     const int64_t first = roff[r] + (g - cpre[r]) * 16;
     const int count = (int)min((int64_t)16, roff[r + 1] - first);
     const PatchDesc pd = descs[r];
@@ -209,14 +204,7 @@ __global__ __launch_bounds__(IM_THREADS) void item_means_kernel(const PatchDesc 
     else th = th_arg;
     const int li = lane & 15, lg = lane >> 4;
     real q[D];
-    if (li < count) {
-        const int64_t qi = item_query[sorted_item[first + li]];
-#pragma unroll
-        for (int d = 0; d < D; ++d) q[d] = (real)xq[qi * D + d];
-    } else {
-#pragma unroll
-        for (int d = 0; d < D; ++d) q[d] = (real)0;
-    }
+    chunk_query_point(first, count, li, sorted_item, item_query, xq, q);
     const real *xs = x + pd.xoff;
     const real *Cb = Cm + pd.yoff * RP + li;
     const int ld = pd.ld, n = pd.n;
@@ -264,8 +252,8 @@ int launch_items_multi(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
 }  // namespace PMK_NS
 
 #ifndef PMK_REAL_F32
-// mix_kernel (pmk_kernels.hip) with R means: the same weights (neighbours phi_w(|t|) in hyperplane order, home 1 last,
-// normalised) and, per column, the same order of operations as its Yq.  Yq is Nq x R column-major (ld Nq).  A row of U
+// mix_kernel (pmk_kernels.hip) with R means: the same weights (blend_weight and blend_weight_sum of pmk_items.h:
+// neighbours phi_w(|t|) in hyperplane order, home 1 last, normalised) and, per column, the same order of operations as its Yq.  Yq is Nq x R column-major (ld Nq).  A row of U
 // has ldu >= R columns (ldu > R with a trend, pmk_trend.hip: the extra columns are not mixed).
 __global__ __launch_bounds__(256) void mix_multi_kernel(int64_t q0, int64_t q1, int64_t Nq, const int64_t *__restrict__ qoff,
                                                         const double *__restrict__ item_t, const int32_t *__restrict__ item_pos,
@@ -275,15 +263,11 @@ __global__ __launch_bounds__(256) void mix_multi_kernel(int64_t q0, int64_t q1, 
     const int64_t j = q0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= q1) return;
     const int64_t b = qoff[j], e = qoff[j + 1];
-    double sw = 0.0;
-    for (int64_t it = b; it < e; ++it) {
-        const double w = (it == e - 1) ? 1.0 : profile(wth, fabs(item_t[it]));
-        sw = (it == b) ? w : sw + w;
-    }
+    const double sw = blend_weight_sum(wth, item_t, b, e);
     for (int col = 0; col < R; ++col) {
         double y = 0.0;
         for (int64_t it = b; it < e; ++it) {
-            const double w = ((it == e - 1) ? 1.0 : profile(wth, fabs(item_t[it]))) / sw;
+            const double w = blend_weight(wth, item_t, it, e) / sw;
             const double ui = U[(int64_t)item_pos[it] * ldu + col];
             y = (it == b) ? w * ui : y + w * ui;
         }
@@ -294,7 +278,7 @@ __global__ __launch_bounds__(256) void mix_multi_kernel(int64_t q0, int64_t q1, 
 int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s)
 {
     if (q1 <= q0) return 0;
-    hipLaunchKernelGGL(mix_multi_kernel, dim3((unsigned)((q1 - q0 + 255) / 256)), dim3(256), 0, s, q0, q1, q->Nq, q->d_qoff,
+    hipLaunchKernelGGL(mix_multi_kernel, grid256(q1 - q0), dim3(256), 0, s, q0, q1, q->Nq, q->d_qoff,
                        q->d_item_t, q->d_item_pos, q->d_um, q->um_ld, q->R_items, wth, q->d_yqm);
     PMK_HIP(hipGetLastError());
     return 0;

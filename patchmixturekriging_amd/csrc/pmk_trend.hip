@@ -25,6 +25,7 @@
 //
 // Every sum over the n rows is taken in double in both precisions with a fixed reduction tree (as evidence_kernel), the
 // small solves run in double in a fixed order, and C is rounded once to the element type.
+#include "pmk_items.h"
 #include "pmk_real.h"
 
 namespace pmk {
@@ -130,11 +131,7 @@ __global__ __launch_bounds__(TG_THREADS) void trend_gls_kernel(const PatchDesc *
         // beta[:, j] = L^-T L^-1 B[:, j], B[a][j] = red[a][j]: thread j < R, forward then backward, in index order
         if (!flag && tid < R) {
             double z[TQ_MAX];
-            for (int a = 0; a < q; ++a) {
-                double t = red[a][tid];
-                for (int k = 0; k < a; ++k) t = __builtin_fma(-sL[a + TQ_MAX * k], z[k], t);
-                z[a] = t / sL[a + TQ_MAX * a];
-            }
+            trend_forward(sL, q, [&](int a) { return red[a][tid]; }, z);
             for (int a = q - 1; a >= 0; --a) {
                 double t = z[a];
                 for (int k = a + 1; k < q; ++k) t = __builtin_fma(-sL[k + TQ_MAX * a], z[k], t);
@@ -183,20 +180,12 @@ __global__ __launch_bounds__(256) void trend_loo_values_kernel(const PatchDesc *
 {
     const int r = blockIdx.x;
     const PatchDesc pd = descs[r];
-    // n <= q: leaving one point out leaves fewer points than basis functions, no such prediction (Q_ii is rounding noise)
-    const bool bad = info[r] != 0 || tinfo[r] != 0 || (q > 0 && pd.n <= q);
+    const bool bad = patch_is_bad_loo(info, tinfo, r, q, pd.n);
     const double nan = __builtin_nan("");
     const double *L = Lg + (int64_t)r * TR_G;
     for (int i = threadIdx.x; i < pd.n; i += 256) {
         const int64_t row = (pd.yoff + i) * TR_RP;
-        double z[TQ_MAX], s = 0.0;
-        for (int a = 0; a < q; ++a) {
-            double t = (double)Cw[row + R + a];
-            for (int k = 0; k < a; ++k) t = __builtin_fma(-L[a + TQ_MAX * k], z[k], t);
-            z[a] = t / L[a + TQ_MAX * a];
-            s = __builtin_fma(z[a], z[a], s);
-        }
-        const double Q = d[pd.yoff + i] - s;
+        const double Q = d[pd.yoff + i] - trend_leverage(L, q, [&](int a) { return (double)Cw[row + R + a]; });
         if (res)
             for (int jj = 0; jj < R; ++jj) res[row + jj] = bad ? nan : (double)Cw[row + jj] / Q;
         if (var) var[pd.yoff + i] = bad ? nan : 1.0 / Q;
@@ -216,8 +205,7 @@ int launch_trend_loo_values(const pmk_model *m, int R, int q, double *d_res, dou
 #ifndef PMK_REAL_F32
 // One thread per sorted item p (row p of U, ld columns: R means, then a = kq^T C_H in columns R .. R + q - 1).
 // Operation order, fixed: rho_a = h_a - a_a for a = 0 .. q - 1; mu_j = fma(h_a, beta[a][j], mu_j) for a = 0 .. q - 1;
-// z_a = (rho_a - sum_{k < a} L[a][k] z_k) / L[a][a] with the sum as an fma chain in k order; add = sum_a z_a^2 as an fma
-// chain in a order; v <- v + add (v has been clamped at min_v before).
+// add = |L_G^-1 rho|^2 (trend_leverage, pmk_items.h); v <- v + add (v has been clamped at min_v before).
 __global__ __launch_bounds__(256) void trend_items_kernel(int64_t total, const int32_t *__restrict__ sorted_item,
                                                           const int32_t *__restrict__ item_region,
                                                           const int32_t *__restrict__ item_query, const double *__restrict__ xq,
@@ -229,7 +217,7 @@ __global__ __launch_bounds__(256) void trend_items_kernel(int64_t total, const i
     if (p >= total) return;
     const int32_t it = sorted_item[p];
     const int64_t r = item_region[it], qi = item_query[it];
-    double h[TQ_MAX], rho[TQ_MAX], z[TQ_MAX];
+    double h[TQ_MAX], rho[TQ_MAX];
     h[0] = 1.0;
     for (int a = 1; a < q; ++a) h[a] = xq[qi * D + (a - 1)];
     double *row = U + p * ld;
@@ -241,14 +229,7 @@ __global__ __launch_bounds__(256) void trend_items_kernel(int64_t total, const i
         row[j] = t;
     }
     if (v) {
-        const double *L = Lg + r * TR_G;
-        double s = 0.0;
-        for (int a = 0; a < q; ++a) {
-            double t = rho[a];
-            for (int k = 0; k < a; ++k) t = __builtin_fma(-L[a + TQ_MAX * k], z[k], t);
-            z[a] = t / L[a + TQ_MAX * a];
-            s = __builtin_fma(z[a], z[a], s);
-        }
+        const double s = trend_leverage(Lg + r * TR_G, q, [&](int a) { return rho[a]; });
         v[p] = v[p] + s;
     }
 }
@@ -257,7 +238,7 @@ int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s
 {
     const pmk_model *m = q->m;
     if (q->total == 0) return 0;
-    hipLaunchKernelGGL(trend_items_kernel, dim3((unsigned)((q->total + 255) / 256)), dim3(256), 0, s, q->total, q->d_sorted_item,
+    hipLaunchKernelGGL(trend_items_kernel, grid256(q->total), dim3(256), 0, s, q->total, q->d_sorted_item,
                        q->d_item_region, q->d_item_query, q->d_xq, m->D, R, qt, q->um_ld, m->d_tbeta, m->d_tL, q->d_um,
                        want_var ? q->d_v : nullptr);
     PMK_HIP(hipGetLastError());
