@@ -81,7 +81,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -506,7 +506,7 @@ int  pmk_query_fetch_multi_dev(pmk_query *q, double *Yq_dev, int64_t ldyq, doubl
  * This is the derivative with the ITEM LIST HELD FIXED.  Where the list changes the blend itself jumps -- at the radius
  * cut-off unless phi_w vanishes there, at a delta test, and where the home leaf changes -- and no derivative exists there.
  * A patch with info != 0, or tinfo != 0 under a trend, gives NaN in all D R values of its items and in every query that
- * blends one of them.  The gradient of the variance is not provided.  Not available through the sharded / all-gather
+ * blends one of them.  The gradient of the variance is the next section.  Not available through the sharded / all-gather
  * exchanges; the model must hold every leaf.  Stage timers "items_grad" and "mix_grad".  A new plan discards the gradients,
  * as it does the items. */
 /* per-item gradients of the items that pmk_query_items_multi or _multi_fitted last computed on this plan.  th: the kernel
@@ -533,6 +533,45 @@ int  pmk_query_get_items_grad(pmk_query *q, double *G, int64_t ldg, int32_t *pla
  * (may be NULL); dYq as in pmk_query_fetch_grad (may be NULL). */
 int  pmk_predict_mixture_grad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                      double radius, double delta, double *Yq, int64_t ldyq, double *dYq, int64_t lddy);
+
+/* ---- gradient of the blended variance of the multi-output path (with or without a trend; fp64 and fp32 models) ----------
+ * Per item (query x, region r), with U_r = K + sigma2 I = L L^T, kq_k = phi(tau_k), g_{d,k} = psi(tau_k) (x_d - z_{k,d}),
+ * V = L^-1 kq, W_d = L^-1 g_d and b = |V|^2: the simple-kriging variance is v_sk = max(k(x,x) - b, min_v), k(x,x) is
+ * constant in x for every family admitted here, and
+ *   d v_sk / dx_d = -2 V . W_d  where k(x,x) - b >= min_v,  exactly 0 where the clamp holds
+ * (decided from the b of the gradient's own sweep).  With a trend of q basis functions v = v_sk + |z|^2, z = L_G^-1 rho,
+ * rho_a = h_a(x) - (kq^T C_H)_a, and the trend adds
+ *   2 z . (L_G^-1 d_d rho),  (d_d rho)_a = [a = 1 + d, linear trend only] - (g_d^T C_H)_a.
+ * The blend is Vq = sum_i wn_i^2 v_i with wn_i = w_i / S (w, S and the item order as above); with the item list held fixed
+ *   dVq/dx_d = sum_i [ wn_i^2 d_d v_i + 2 wn_i v_i d_d wn_i ],  d_d wn_i = (d_d w_i - wn_i sum_j d_d w_j) / S,
+ * d_d w_i as in the gradient of the mean.  The same caveat holds: where the item list changes the blend jumps and has no
+ * derivative.  An item's D values have the same bits whatever other items share its strip and wherever it sits in it.  A
+ * patch with info != 0, or tinfo != 0 under a trend, gives NaN in all D values of its items and in every query that blends
+ * one of them.  No route of this interface sets a query's min_v (it is 1e-12), so the clamp needs k(x,x) - b < 1e-12.
+ * No sharded or all-gather form; the model must hold every leaf.  Stage timers "items_vgrad" and "mix_vgrad".  A new plan
+ * or new items discard the results. */
+/* per-item variance gradients of the items that pmk_query_items_multi or _multi_fitted last computed on this plan WITH
+ * want_var = 1.  th: the kernel for every patch, or NULL for the model's own kernels (-3 if it holds none).  Enqueues only.
+ * The refusals of pmk_query_items_grad, and -2 also after items with want_var = 0 and for a query that carries
+ * pmk_query_set_diag addends (their dependence on x is unknown to the library); -3: stale multi-output weights. */
+int  pmk_query_items_vgrad(pmk_query *q, const pmk_kernel_desc *th);
+/* the gradient of the blended variance for queries [q0, q1), weight_th as in pmk_query_mix_grad.  Enqueues.  -2 before
+ * pmk_query_items_vgrad has run on this plan. */
+int  pmk_query_mix_vgrad(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1);
+/* blocks; dVq[j + lddv * d] = dVq/dx_d at query j, lddv >= Nq.  -2 before pmk_query_mix_vgrad. */
+int  pmk_query_fetch_vgrad(pmk_query *q, double *dVq, int64_t lddv);
+/* the same into a DEVICE array: device-to-device on the context's stream, no host synchronisation */
+int  pmk_query_fetch_vgrad_dev(pmk_query *q, double *dVq_dev, int64_t lddv);
+/* the per-item gradients GV[i * ldg + d] (ldg >= D), items in the order of pmk_query_debug.  -2 before
+ * pmk_query_items_vgrad.  Blocks. */
+int  pmk_query_get_items_vgrad(pmk_query *q, double *GV, int64_t ldg);
+/* one-shot: create + plan + pmk_query_items_multi_fitted with the variance + pmk_query_items_grad(NULL) +
+ * pmk_query_items_vgrad(NULL) + pmk_query_mix_multi + pmk_query_mix_grad + pmk_query_mix_vgrad + the fetches.  Yq: Nq x R
+ * column-major, ldyq >= Nq; Vq: Nq; dYq as in pmk_query_fetch_grad; dVq as in pmk_query_fetch_vgrad.  Any output pointer
+ * may be NULL. */
+int  pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                      double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *dYq,
+                                      int64_t lddy, double *dVq, int64_t lddv);
 
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,

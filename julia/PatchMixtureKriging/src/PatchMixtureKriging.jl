@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad
+       querymixtureGP_grad, querymixtureGP_vgrad
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -971,6 +971,57 @@ function querymixtureGP_grad(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Floa
         check(ccall((:pmk_query_get_items_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int32}), q[], G, D * R, plane),
               "pmk_query_get_items_grad")
         return Yq, dYq, G, Int.(plane) .+ 1
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""querymixtureGP_vgrad(Xq, η, root, levels, radius, δ, weight_θ; items = false) -> (Yq, Vq, dYq, dVq): querymixtureGP_grad's
+blended means and their gradient, the blended variance Vq (Nq) and its gradient dVq[j, d] = ∂Vq/∂x_d at query j (Nq x D),
+with the model's own kernels and its trend if one is set (pmk_predict_mixture_vgrad_fitted).  The derivative holds the item
+list of each query fixed.  Brownian-bridge kernels are refused.  items = true runs the staged calls and also returns GV,
+D x total: the per-item variance gradients in the item order of the plan."""
+function querymixtureGP_vgrad(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float64}, root, levels, radius::Float64, δ::Float64,
+                              weight_θ; items::Bool = false)
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_vgrad"))
+    R = η.R_multi
+    R >= 1 || throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_vgrad"))
+    Nq = length(Xq); Xm = array2matrix(Xq); D = size(Xm, 1)
+    Yq = Matrix{Float64}(undef, Nq, R); dYq = Array{Float64,3}(undef, Nq, D, R)
+    Vq = Vector{Float64}(undef, Nq); dVq = Matrix{Float64}(undef, Nq, D)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    if !items
+        check(ccall((:pmk_predict_mixture_vgrad_fitted, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64},
+                     Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+                    η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Yq, max(Nq, 1), Vq, dYq, max(Nq, 1), dVq, max(Nq, 1)),
+              "pmk_predict_mixture_vgrad_fitted")
+        return Yq, Vq, dYq, dVq
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL); total = Ref{Int64}(0)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_counts, libpmk), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}), q[], total,
+                    Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL)), "pmk_query_counts")
+        check(ccall((:pmk_query_items_multi_fitted, libpmk), Cint, (Ptr{Cvoid}, Cint), q[], 1), "pmk_query_items_multi_fitted")
+        check(ccall((:pmk_query_items_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}), q[], Ptr{KernelDesc}(C_NULL)),
+              "pmk_query_items_grad")
+        check(ccall((:pmk_query_items_vgrad, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}), q[], Ptr{KernelDesc}(C_NULL)),
+              "pmk_query_items_vgrad")
+        check(ccall((:pmk_query_mix_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_multi")
+        check(ccall((:pmk_query_mix_grad, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_grad")
+        check(ccall((:pmk_query_mix_vgrad, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_vgrad")
+        check(ccall((:pmk_query_fetch_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], Yq, max(Nq, 1), Vq),
+              "pmk_query_fetch_multi")
+        check(ccall((:pmk_query_fetch_grad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], dYq, max(Nq, 1)), "pmk_query_fetch_grad")
+        check(ccall((:pmk_query_fetch_vgrad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], dVq, max(Nq, 1)), "pmk_query_fetch_vgrad")
+        GV = Matrix{Float64}(undef, D, total[])
+        check(ccall((:pmk_query_get_items_vgrad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], GV, D), "pmk_query_get_items_vgrad")
+        return Yq, Vq, dYq, dVq, GV
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end

@@ -279,6 +279,7 @@ void pmk_query_destroy(pmk_query *q)
     if (q->d_tasks) (void)hipFree(q->d_tasks);
     if (q->d_sync) (void)hipFree(q->d_sync);
     dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre); dev_free(q->d_gm); dev_free(q->d_dyq);
+    dev_free(q->d_gv); dev_free(q->d_gh); dev_free(q->d_dvq); dev_free(q->d_vgpre);
     dev_free(q->d_loo_x);               // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
@@ -496,6 +497,20 @@ static int fetch_multi_common(pmk_query *q, double *Yq, int64_t ldyq, double *Vq
                                      sizeof(double) * (size_t)q->Nq, (size_t)q->R_items, kind, c->stream));
         if (Vq) PMK_HIP(hipMemcpyAsync(Vq, q->d_vq, sizeof(double) * (size_t)q->Nq, kind, c->stream));
     }
+    return 0;
+}
+
+static int fetch_vgrad_common(pmk_query *q, double *dVq, int64_t lddv, hipMemcpyKind kind, const char *who)
+{
+    if (!q) { set_error("%s: query is NULL", who); return -1; }
+    if (!q->mixed_vgrad || !q->vgrad_items) { set_error("%s: pmk_query_mix_vgrad has not run", who); return -2; }
+    if (!dVq) { set_error("%s: dVq is NULL", who); return -2; }
+    if (lddv < q->Nq) { set_error("%s: lddv = %lld < Nq = %lld", who, (long long)lddv, (long long)q->Nq); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0)
+        PMK_HIP(hipMemcpy2DAsync(dVq, sizeof(double) * (size_t)lddv, q->d_dvq, sizeof(double) * (size_t)q->Nq,
+                                 sizeof(double) * (size_t)q->Nq, (size_t)q->m->D, kind, c->stream));
     return 0;
 }
 
@@ -842,6 +857,132 @@ int pmk_predict_mixture_grad_fitted(pmk_model *m, const pmk_kernel_desc *weight_
         [&](pmk_query *q) {
             int rc = Yq ? pmk_query_fetch_multi(q, Yq, ldyq, nullptr) : 0;
             return !rc && dYq ? pmk_query_fetch_grad(q, dYq, lddy) : rc;
+        });
+}
+
+// ------------------------------------------------------------------------------------------ gradient of the blended variance
+int pmk_query_items_vgrad(pmk_query *q, const pmk_kernel_desc *th)
+{
+    if (!q || !q->planned) { set_error("pmk_query_items_vgrad: query is not planned"); return -1; }
+    pmk_model *m = q->m;
+    if (int rc = whole_tree_ok(m, "pmk_query_items_vgrad", GRAD_NEEDS_ALL, -4)) return rc;
+    if (!m->multi_solved) {
+        set_error("pmk_query_items_vgrad: pmk_model_solve_multi has not run on the resident factor");
+        return -3;
+    }
+    if (q->R_items < 1 || !q->items_fn || !q->var_items) {
+        set_error("pmk_query_items_vgrad: the last items on this plan must be those of pmk_query_items_multi or "
+                  "_multi_fitted with want_var = 1 (a member item of pmk_query_items_loo_multi is a lookup, not a function "
+                  "of x)");
+        return -2;
+    }
+    if (q->d_qdiag) {
+        set_error("pmk_query_items_vgrad: the query carries pmk_query_set_diag addends, whose dependence on x the library "
+                  "does not know");
+        return -2;
+    }
+    if (th) {
+        if (int rc = grad_kernel_ok(th, m->D, "pmk_query_items_vgrad", "theta")) return rc;
+    } else {
+        if (m->ths.empty()) { set_error("pmk_query_items_vgrad: the model holds no kernels (pmk_model_set_kernels)"); return -3; }
+        for (size_t r = 0; r < m->ths.size(); ++r)
+            if (int rc = grad_kernel_ok(&m->ths[r], m->D, "pmk_query_items_vgrad", "the model's own theta")) return rc;
+        th = fitted_theta(m);
+    }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    q->vgrad_items = q->mixed_vgrad = false;
+    // strips per region: the host prefix the kernel finds its region by (q->vgpre stays: it is the source of the upload)
+    const int64_t cap = vgrad_strip_items(m->D);
+    q->vgpre.assign((size_t)m->P + 1, 0);
+    for (int64_t r = 0; r < m->P; ++r)
+        q->vgpre[(size_t)r + 1] = q->vgpre[(size_t)r] + (q->roff[(size_t)r + 1] - q->roff[(size_t)r] + cap - 1) / cap;
+    q->vstrips = q->vgpre[(size_t)m->P];
+    if (int rc = grow(q->d_vgpre, q->vgpre_cap, m->P + 1, s)) return rc;
+    if (int rc = grow(q->d_gv, q->gv_cap, q->total * m->D, s)) return rc;
+    if (int rc = grow(q->d_gh, q->gh_cap, q->total * m->D * m->trend_q, s)) return rc;
+    PMK_HIP(hipMemcpyAsync(q->d_vgpre, q->vgpre.data(), sizeof(int64_t) * q->vgpre.size(), hipMemcpyHostToDevice, s));
+    c->tic("items_vgrad");
+    int rc = PMK_BY_DTYPE(m, launch_items_vgrad(q, th, s));
+    if (!rc) rc = launch_trend_vgrad(q, s);
+    c->toc("items_vgrad");
+    if (rc) return rc;
+    q->vgrad_items = true;
+    return 0;
+}
+
+int pmk_query_mix_vgrad(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t q0, int64_t q1)
+{
+    if (!q || !q->planned) { set_error("pmk_query_mix_vgrad: query is not planned"); return -1; }
+    if (!q->vgrad_items || !q->var_items) { set_error("pmk_query_mix_vgrad: pmk_query_items_vgrad has not run on this plan"); return -2; }
+    if (int rc = grad_kernel_ok(weight_th, 1, "pmk_query_mix_vgrad", "the blending profile")) return rc;
+    if (int rc = query_range_ok(q, q0, q1, "pmk_query_mix_vgrad")) return rc;
+    pmk_model *m = q->m;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (int rc = grow(q->d_dvq, q->dvq_cap, q->Nq * m->D, c->stream)) return rc;
+    c->tic("mix_vgrad");
+    const int rc = launch_mix_vgrad(q, *weight_th, q0, q1, c->stream);
+    c->toc("mix_vgrad");
+    if (rc) return rc;
+    q->mixed_vgrad = true;
+    return 0;
+}
+
+int pmk_query_fetch_vgrad(pmk_query *q, double *dVq, int64_t lddv)
+{
+    if (int rc = fetch_vgrad_common(q, dVq, lddv, hipMemcpyDeviceToHost, "pmk_query_fetch_vgrad")) return rc;
+    PMK_HIP(hipStreamSynchronize(q->m->ctx->stream));
+    return 0;
+}
+
+int pmk_query_fetch_vgrad_dev(pmk_query *q, double *dVq_dev, int64_t lddv)
+{
+    return fetch_vgrad_common(q, dVq_dev, lddv, hipMemcpyDeviceToDevice, "pmk_query_fetch_vgrad_dev");
+}
+
+int pmk_query_get_items_vgrad(pmk_query *q, double *GV, int64_t ldg)
+{
+    if (!q || !q->planned) { set_error("pmk_query_get_items_vgrad: query is not planned"); return -1; }
+    if (!q->vgrad_items) { set_error("pmk_query_get_items_vgrad: pmk_query_items_vgrad has not run on this plan"); return -2; }
+    if (!GV) { set_error("pmk_query_get_items_vgrad: GV is NULL"); return -2; }
+    const size_t D = (size_t)q->m->D;
+    if (ldg < (int64_t)D) { set_error("pmk_query_get_items_vgrad: ldg = %lld < D = %lld", (long long)ldg, (long long)D); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    if (q->total == 0) return 0;
+    return download_item_rows(q, q->d_gv, D, D, GV, (size_t)ldg);
+}
+
+int pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                     double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *dYq,
+                                     int64_t lddy, double *dVq, int64_t lddv)
+{
+    if (!m) { set_error("pmk_predict_mixture_vgrad_fitted: model is NULL"); return -1; }
+    if (int rc = whole_tree_ok(m, "pmk_predict_mixture_vgrad_fitted", GRAD_NEEDS_ALL, -4)) return rc;
+    if ((Yq && ldyq < Nq) || (dYq && lddy < Nq) || (dVq && lddv < Nq)) {
+        set_error("pmk_predict_mixture_vgrad_fitted: ldyq = %lld, lddy = %lld or lddv = %lld < Nq = %lld", (long long)ldyq,
+                  (long long)lddy, (long long)lddv, (long long)Nq);
+        return -4;
+    }
+    return one_shot(
+        m, Nq, Xq, radius, delta,
+        [&](pmk_query *q) {
+            int rc = pmk_query_items_multi_fitted(q, 1);
+            if (!rc) rc = pmk_query_items_grad(q, nullptr);
+            return rc ? rc : pmk_query_items_vgrad(q, nullptr);
+        },
+        [&](pmk_query *q) {
+            int rc = pmk_query_mix_multi(q, weight_th, 0, Nq);
+            if (!rc) rc = pmk_query_mix_grad(q, weight_th, 0, Nq);
+            return rc ? rc : pmk_query_mix_vgrad(q, weight_th, 0, Nq);
+        },
+        [&](pmk_query *q) {
+            int rc = (Yq || Vq) ? pmk_query_fetch_multi(q, Yq, ldyq, Vq) : 0;
+            if (!rc && dYq) rc = pmk_query_fetch_grad(q, dYq, lddy);
+            return !rc && dVq ? pmk_query_fetch_vgrad(q, dVq, lddv) : rc;
         });
 }
 

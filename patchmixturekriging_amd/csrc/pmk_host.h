@@ -122,6 +122,7 @@ inline void reset_item_state(pmk_query *q)
     q->R_items = 0;
     q->mixed_multi = false;
     q->items_fn = q->grad_items = q->mixed_grad = false;
+    q->vgrad_items = q->mixed_vgrad = false;
 }
 
 // The one-shot calls: a query object for Xq, its plan, the three stages as the caller gives them, and the object goes

@@ -17,6 +17,9 @@ constexpr int TQ = 256;         // query columns per prediction strip (8 waves x
 // layout of the per-patch trend state and of the multi-output blocks, shared by pmk_trend.hip and pmk_loo_mix.hip
 constexpr int TQ_MAX = 1 + MAX_D;             // basis functions of the linear trend at D = 4; leading dimension of L_G
 constexpr int TR_RP = PMK_MAX_OUTPUTS;        // columns of a row of the target / weight block
+// items of a strip of the variance-gradient sweep (pmk_vgrad.hip): an item takes D + 1 of the 16 lanes of a row, a lane
+// holds two columns, a strip eight waves: 128 / 80 / 64 / 48 at D = 1 / 2 / 3 / 4
+constexpr int vgrad_strip_items(int D) { return 8 * 2 * (16 / (D + 1)); }
 
 void set_error(const char *fmt, ...);
 
@@ -222,6 +225,13 @@ struct pmk_query {
     bool items_fn = false, grad_items = false, mixed_grad = false;
     double *d_gm = nullptr; int64_t gm_cap = 0;       // sorted items x (D x R_items): G[p][d + D c]
     double *d_dyq = nullptr; int64_t dyq_cap = 0;     // Nq x (D x R_items) column-major: dYq[j + Nq (d + D c)]
+    // gradient of the blended variance (pmk_vgrad.hip), on items computed with want_var = 1; discarded like the above
+    bool vgrad_items = false, mixed_vgrad = false;
+    double *d_gv = nullptr; int64_t gv_cap = 0;       // sorted items x D: GV[p][d]
+    double *d_gh = nullptr; int64_t gh_cap = 0;       // sorted items x (D x q), under a trend: GH[p][a + q d] = (g_d^T C_H)_a
+    double *d_dvq = nullptr; int64_t dvq_cap = 0;     // Nq x D column-major: dVq[j + Nq d]
+    int64_t *d_vgpre = nullptr; int64_t vgpre_cap = 0, vstrips = 0;   // strips of vgrad_strip_items(D) items per region: prefix [P+1]
+    std::vector<int64_t> vgpre;         // host copy (source of the upload)
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -273,6 +283,7 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
                            const double *d_rv, hipStream_t s);                                                       \
     int launch_loo_member_multi(pmk_query *q, int noisy, int want_var, int32_t *d_mark, hipStream_t s);              \
     int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                   \
+    int launch_items_vgrad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -294,6 +305,8 @@ int launch_mix(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1,
 int launch_mix_multi(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s);
 int launch_mix_grad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
+int launch_trend_vgrad(pmk_query *q, hipStream_t s);
+int launch_mix_vgrad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
                              const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);

@@ -38,6 +38,7 @@ static int no_gpu(const char *what)
     int launch_loo_scatter(pmk_query *, int, const int32_t *, const int64_t *, const double *, const double *, hipStream_t) { return no_gpu("launch_loo_scatter"); } \
     int launch_loo_member_multi(pmk_query *, int, int, int32_t *, hipStream_t) { return no_gpu("launch_loo_member_multi"); } \
     int launch_items_grad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_grad"); } \
+    int launch_items_vgrad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_vgrad"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -53,6 +54,8 @@ int launch_mix(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream
 int launch_mix_multi(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_multi"); }
 int launch_trend_items(pmk_query *, int, int, bool, hipStream_t) { return no_gpu("launch_trend_items"); }
 int launch_mix_grad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_grad"); }
+int launch_trend_vgrad(pmk_query *, hipStream_t) { return no_gpu("launch_trend_vgrad"); }
+int launch_mix_vgrad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_vgrad"); }
 int launch_loo_scatter_multi(pmk_query *, const pmk_query *, int, int, const int32_t *, const int64_t *, hipStream_t)
 {
     return no_gpu("launch_loo_scatter_multi");

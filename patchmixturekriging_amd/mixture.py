@@ -542,7 +542,7 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_counts(self.h, C.byref(t), C.byref(f), C.byref(o)))
         self.total, self.first_owned, self.num_owned = t.value, f.value, o.value
         self.R_items = 0                    # a new plan discards the items, as in the library
-        self.grad_items = False
+        self.grad_items = self.vgrad_items = False
         return self.total
 
     def region_offsets(self, P_global):
@@ -599,7 +599,7 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_items_loo_multi(self.h, int(bool(noisy)), int(bool(variance)), C.byref(nm), C.byref(no)),
                    "pmk_query_items_loo_multi")
         self.variance, self.R_items = bool(variance), int(m.R)
-        self.grad_items = False
+        self.grad_items = self.vgrad_items = False
         return nm.value, no.value
 
     def item_values_multi(self):
@@ -621,7 +621,7 @@ class DeviceQuery:
             raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
         _lib.check(self.L.pmk_query_items_multi_fitted(self.h, int(bool(variance))), "pmk_query_items_multi_fitted")
         self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
-        self.grad_items = False
+        self.grad_items = self.vgrad_items = False
 
     def item_buffers(self):
         u, v = C.c_void_p(), C.c_void_p()
@@ -690,7 +690,7 @@ class DeviceQuery:
         d = theta.desc()
         _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
         self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
-        self.grad_items = False
+        self.grad_items = self.vgrad_items = False
 
     def mix_multi(self, weight_theta, q0=0, q1=None):
         d = weight_theta.desc()
@@ -755,6 +755,55 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_get_items_grad(self.h, None if G is None else _d(G), R * D,
                                                    plane.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_query_get_items_grad")
         return (None if G is None else G[:self.total]), plane[:self.total]
+
+    # ---- gradient of the blended variance (pmk_vgrad.hip)
+    def items_vgrad(self, theta=None):
+        """pmk_query_items_vgrad: the gradient of every item variance of the last items_multi / items_multi_fitted on this
+        plan, which must have run with the variance; `theta` for every patch or (None) the model's own kernels.  A query
+        with set_diag addends is refused.  Closure-carrying kernels raise TypeError and Brownian-bridge kernels ValueError
+        before any device call."""
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            d = _grad_kernel(theta, "items_vgrad")
+            ptr = C.byref(d)
+        _lib.check(self.L.pmk_query_items_vgrad(self.h, ptr), "pmk_query_items_vgrad")
+        self.vgrad_items = True
+
+    def mix_vgrad(self, weight_theta, q0=0, q1=None):
+        """pmk_query_mix_vgrad: the gradient of the blended variance of mix_multi for queries [q0, q1), the item list held
+        fixed"""
+        d = _grad_kernel(weight_theta, "mix_vgrad")
+        _lib.check(self.L.pmk_query_mix_vgrad(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
+                   "pmk_query_mix_vgrad")
+
+    def fetch_vgrad(self):
+        """dVq [Nq, D]: dVq[j, d] = dVq/dx_d at query j"""
+        D = int(self.model.D)
+        buf = np.empty((D, max(self.Nq, 1)))                    # dVq[j + lddv d]
+        _lib.check(self.L.pmk_query_fetch_vgrad(self.h, _d(buf), max(self.Nq, 1)), "pmk_query_fetch_vgrad")
+        return np.ascontiguousarray(buf[:, :self.Nq].T)
+
+    def fetch_vgrad_into(self, dVq):
+        """pmk_query_fetch_vgrad_dev: dVq is a device array of shape (D, Nq), C-contiguous (element [d, j] is dVq/dx_d at
+        query j): device-to-device on the context's stream, no host synchronisation"""
+        D = int(self.model.D)
+        ga = self._device_out(dVq, "dVq")
+        if ga.shape != (D, self.Nq) or (self.Nq > 0 and ga.strides != (self.Nq, 1)):
+            raise ValueError("dVq must be a C-contiguous device array of shape (%d, %d), not %s" % (D, self.Nq, ga.shape))
+        _lib.check(self.L.pmk_query_fetch_vgrad_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_vgrad_dev")
+
+    def item_vgrads(self):
+        """pmk_query_get_items_vgrad -> GV [total, D] in the item order of debug(): GV[i, d] is the gradient of item i's
+        variance"""
+        if not getattr(self, "vgrad_items", False):
+            raise _lib.PmkError("item_vgrads: items_vgrad has not run on this plan")
+        D = int(self.model.D)
+        GV = np.empty((max(int(self.total), 1), D))
+        _lib.check(self.L.pmk_query_get_items_vgrad(self.h, _d(GV), D), "pmk_query_get_items_vgrad")
+        return GV[:self.total]
 
     def debug(self):
         home = np.empty(self.Nq, dtype=np.int64)
@@ -1131,12 +1180,14 @@ def querymixtureGP_multi(Xq, eta, root, levels, radius, delta, theta, sigma2, we
     return q.fetch_multi(model.R)
 
 
-def querymixtureGP_grad(Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta):
+def querymixtureGP_grad(Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta, variance=False):
     """querymixtureGP_multi's blended means and their gradient -> (Yq [Nq, R], dYq [Nq, R, D]), dYq[j, c, d] = dY_c/dx_d,
     for the R columns of fitmixtureGP_multi_ or fitmixtureGP_trend_.  No triangular solve runs.  The derivative holds each
     query's item list fixed: where the list changes (the radius cut-off unless the weight profile vanishes there, a delta
     test, a change of home leaf) the blend itself jumps and has no derivative.  Closure-carrying kernels raise TypeError,
-    Brownian-bridge kernels ValueError, before any device call."""
+    Brownian-bridge kernels ValueError, before any device call.
+    variance=True: also the blended variance and its gradient -> (Yq, Vq [Nq], dYq, dVq [Nq, D]), dVq[j, d] = dVq/dx_d;
+    the strip kernel runs for the variance and the strip sweep with D + 1 right-hand sides for its gradient."""
     _grad_kernel(theta, "querymixtureGP_grad")
     _grad_kernel(weight_theta, "querymixtureGP_grad")
     if eta._model is None or getattr(eta, "C_set", None) is None:
@@ -1149,11 +1200,17 @@ def querymixtureGP_grad(Xq, eta, root, levels, radius, delta, theta, sigma2, wei
     model.set_bsp(root, 0)
     q = DeviceQuery(model, Xq)
     q.plan(radius, delta)
-    q.items_multi(theta, False)
+    q.items_multi(theta, bool(variance))
     q.items_grad(theta)
+    if variance:
+        q.items_vgrad(theta)
     q.mix_multi(weight_theta)
     q.mix_grad(weight_theta)
-    return q.fetch_multi(model.R)[0], q.fetch_grad()
+    if not variance:
+        return q.fetch_multi(model.R)[0], q.fetch_grad()
+    q.mix_vgrad(weight_theta)
+    Yq, Vq = q.fetch_multi(model.R)
+    return Yq, Vq, q.fetch_grad(), q.fetch_vgrad()
 
 
 # ---- model selection: is this (theta, sigma2) any good on this patch?  The reference picks both by hand
