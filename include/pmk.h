@@ -34,6 +34,7 @@ extern "C" {
 
 #define PMK_VERSION 103
 #define PMK_MAX_OUTPUTS 16   /* target columns per patch of the multi-output entry points (pmk_model_set_targets_multi) */
+#define PMK_COV_MAX_QUERIES 16384   /* queries of a batch whose joint covariance is asked for (pmk_query_items_cov) */
 
 /* kernel families = the isbits kernel structs of src/misc/declarations.jl:18-45,65-67,75-111 */
 enum {
@@ -81,7 +82,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad", "items_cov", "mix_cov"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -572,6 +573,47 @@ int  pmk_query_get_items_vgrad(pmk_query *q, double *GV, int64_t ldg);
 int  pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                       double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *dYq,
                                       int64_t lddy, double *dVq, int64_t lddv);
+
+/* ---- joint posterior covariance of a query batch under the blend (single-output path; fp64 and fp32 models) ---------------
+ * The patches are independent GPs, so with V_{r,j} = L_r^-1 k_r(X_r, x_j) and wn the normalised weights of pmk_query_mix
+ *   Cov[j, j'] = sum over the regions r that hold an item of BOTH j and j':
+ *                wn_{r,j} wn_{r,j'} ( k_r(x_j, x_j') - V_{r,j} . V_{r,j'} ).
+ * For j = j' this is Vq = sum wn^2 v.  Per region r with m_r items the stage computes the block
+ *   S_r[a, b] = k_r(x_a, x_b) - V_a . V_b                                             for a != b (not clamped),
+ *   S_r[a, a] = max( k_r(x_a, x_a) + the addend of pmk_query_set_diag - |V_a|^2, min_v ),
+ * the rows being the region's items in ascending query index.  The neighbour search can accept one leaf through two
+ * hyperplanes; such a query holds two items (two rows) of the region, every pair of items of j and j' in a common region
+ * is a term of Cov[j, j'], and its diagonal entry carries the cross term that Vq does not.  Entry (a, b) of a block has the same bits whatever else is
+ * in the batch; blocks and result are symmetric bit for bit and the same from run to run; queries that share no region
+ * give exact zeros.  A patch with info != 0 gives NaN in its whole block and in the whole row and column of every query
+ * that blends one of its items.  This is the single-output path: it ignores the trend, as pmk_query_items does, and does
+ * not depend on targets; it needs a resident factor only, so models of pmk_model_load + pmk_model_set_kernels serve too.
+ * Out of scope: a trend's term z . z', the sharded and all-gather exchanges (the model must hold every leaf), and fusing
+ * the means into the covariance sweep.  Every family is admitted (nothing here differentiates), PMK_MODSQEXP at D = 1 only.
+ * Memory, owned by the query, grow only: sum over strips of ld x 256 elements of the model's type (a region's items are
+ * dealt over ceil(m_r / 256) strips, ld the padded size of its patch), 8 sum m_r^2 bytes of blocks and 8 Nq^2 bytes of
+ * result; a failed allocation returns -100 with the bytes asked for in the text.  Stage timers "items_cov" (sweep, Gram and
+ * blocks) and "mix_cov".  A new plan discards the results.  At most PMK_COV_MAX_QUERIES queries a batch. */
+/* the region blocks of the current plan.  th: the kernel for every patch, or NULL for the model's own kernels.  Enqueues.
+ * Serves a query made by pmk_query_create_items too (the joint form of pmk_model_queryinner for a patch).  -1: no plan or
+ * no resident factor; -2: unknown family, PMK_MODSQEXP with D > 1; -3: th NULL on a model that holds no kernels, or the
+ * model does not hold every leaf; -5: Nq > PMK_COV_MAX_QUERIES. */
+int  pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th);
+/* the blend of the whole batch, weight_th as in pmk_query_mix.  Enqueues.  -2 before pmk_query_items_cov has run on this
+ * plan, and on a query made by pmk_query_create_items. */
+int  pmk_query_mix_cov(pmk_query *q, const pmk_kernel_desc *weight_th);
+/* blocks; Cov[j + ldc * j'], Nq x Nq column-major, ldc >= Nq.  -2 before pmk_query_mix_cov. */
+int  pmk_query_fetch_cov(pmk_query *q, double *Cov, int64_t ldc);
+/* the same into a DEVICE array: device-to-device on the context's stream, no host synchronisation */
+int  pmk_query_fetch_cov_dev(pmk_query *q, double *Cov_dev, int64_t ldc);
+/* the block of one global region: *m its item count, query[m] the query index of each row (ascending), S m x m
+ * column-major with lds >= m.  Any pointer may be NULL, so a first call can size the buffers.  Blocks.  -2 before
+ * pmk_query_items_cov; -3: the region is not one of the model's leaves. */
+int  pmk_query_get_items_cov(pmk_query *q, int64_t region, int64_t *m, int32_t *query, double *S, int64_t lds);
+/* one-shot: create + plan + pmk_query_items_fitted + pmk_query_mix + pmk_query_items_cov(NULL) + pmk_query_mix_cov + the
+ * fetches.  Any output pointer may be NULL; with Cov NULL no covariance stage runs. */
+int  pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                    double radius, double delta, double *Yq, double *Vq, double *Cov, int64_t ldc);
 
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,

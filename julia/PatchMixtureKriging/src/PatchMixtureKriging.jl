@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -1022,6 +1022,55 @@ function querymixtureGP_vgrad(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Flo
         GV = Matrix{Float64}(undef, D, total[])
         check(ccall((:pmk_query_get_items_vgrad, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], GV, D), "pmk_query_get_items_vgrad")
         return Yq, Vq, dYq, dVq, GV
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""querymixtureGP_cov(Xq, η, root, levels, radius, δ, weight_θ; region = 0, device = C_NULL) -> (Yq, Vq, Cov): the blended
+mean and variance of querymixtureGP with the model's own kernels and the joint posterior covariance Cov (Nq x Nq, symmetric)
+of the batch under the blend (pmk_predict_mixture_cov_fitted).  Queries that share no region have covariance exactly 0.
+Single-output path, no trend; at most 16384 queries.  region = r > 0 runs the staged calls and also returns (query, S): the
+posterior covariance block of region r over its items and the 1-based query index of each of its rows.  device: a device
+pointer to Nq x Nq Float64 that receives Cov as well (pmk_query_fetch_cov_dev; staged calls)."""
+function querymixtureGP_cov(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float64}, root, levels, radius::Float64, δ::Float64,
+                            weight_θ; region::Int = 0, device::Ptr{Float64} = Ptr{Float64}(C_NULL))
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before querymixtureGP_cov"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    Yq = Vector{Float64}(undef, Nq); Vq = Vector{Float64}(undef, Nq); Cov = Matrix{Float64}(undef, Nq, Nq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    if region == 0 && device == C_NULL
+        check(ccall((:pmk_predict_mixture_cov_fitted, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Int64),
+                    η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Yq, Vq, Cov, max(Nq, 1)),
+              "pmk_predict_mixture_cov_fitted")
+        return Yq, Vq, Cov
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_items_fitted, libpmk), Cint, (Ptr{Cvoid},), q[]), "pmk_query_items_fitted")
+        check(ccall((:pmk_query_mix, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix")
+        check(ccall((:pmk_query_items_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}), q[], Ptr{KernelDesc}(C_NULL)),
+              "pmk_query_items_cov")
+        check(ccall((:pmk_query_mix_cov, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}), q[], Ref(desc(weight_θ))), "pmk_query_mix_cov")
+        check(ccall((:pmk_query_fetch, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), q[], Yq, Vq), "pmk_query_fetch")
+        check(ccall((:pmk_query_fetch_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], Cov, max(Nq, 1)), "pmk_query_fetch_cov")
+        if device != C_NULL
+            check(ccall((:pmk_query_fetch_cov_dev, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], device, max(Nq, 1)),
+                  "pmk_query_fetch_cov_dev")
+        end
+        region == 0 && return Yq, Vq, Cov
+        m = Ref{Int64}(0)
+        check(ccall((:pmk_query_get_items_cov, libpmk), Cint, (Ptr{Cvoid}, Int64, Ref{Int64}, Ptr{Int32}, Ptr{Float64}, Int64),
+                    q[], region - 1, m, Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL), 0), "pmk_query_get_items_cov")
+        query = Vector{Int32}(undef, m[]); S = Matrix{Float64}(undef, m[], m[])
+        check(ccall((:pmk_query_get_items_cov, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64),
+                    q[], region - 1, Ptr{Int64}(C_NULL), query, S, max(m[], 1)), "pmk_query_get_items_cov")
+        return Yq, Vq, Cov, query .+ Int32(1), S
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end

@@ -19,7 +19,7 @@ from .mixture import (DeviceModel, DeviceQuery, MixtureGPDebugType, MixtureGPTyp
                       querymixtureGP_, querymixtureGP_multi, fitmixtureGP_patches_, querymixtureGP_patches,
                       querymixtureGP_multi_patches, select_candidates, selectmixtureGP_, fitmixtureGP_trend_,
                       TrendRankException, loomixtureGP_blend, selectblendGP_, loomixtureGP_blend_multi,
-                      selectblendGP_multi_, querymixtureGP_grad)
+                      selectblendGP_multi_, querymixtureGP_grad, querymixtureGP_cov, samplemixtureGP)
 from .partition import (BinaryNode, HyperplaneType, PartitionDataType, array2matrix,  # noqa: F401
                         convert2itpindex, fetchhyperplanes, findneighbourpartitions, findpartition,
                         getpartitionlines_,

@@ -183,6 +183,13 @@ SIGNATURES = {
     "pmk_query_get_items_vgrad": (C.c_int, [_vp, _dp, C.c_int64]),
     "pmk_predict_mixture_vgrad_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64, _dp,
                                                    _dp, C.c_int64, _dp, C.c_int64]),
+    "pmk_query_items_cov": (C.c_int, [_vp, _kp]),
+    "pmk_query_mix_cov": (C.c_int, [_vp, _kp]),
+    "pmk_query_fetch_cov": (C.c_int, [_vp, _dp, C.c_int64]),
+    "pmk_query_fetch_cov_dev": (C.c_int, [_vp, C.c_void_p, C.c_int64]),
+    "pmk_query_get_items_cov": (C.c_int, [_vp, C.c_int64, _ip, _i32p, _dp, C.c_int64]),
+    "pmk_predict_mixture_cov_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp, _dp,
+                                                 C.c_int64]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

@@ -67,7 +67,8 @@ int query_set_items(pmk_query *q, int64_t n, const double *xq, const int32_t *re
     q->Nq = n;
     q->total = n;
     q->planned = false;
-    reset_item_state(q);
+    reset_plan_state(q);
+    q->explicit_items = true;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     q->ntasks = 0;
     if (n > 0) {
@@ -280,6 +281,8 @@ void pmk_query_destroy(pmk_query *q)
     if (q->d_sync) (void)hipFree(q->d_sync);
     dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre); dev_free(q->d_gm); dev_free(q->d_dyq);
     dev_free(q->d_gv); dev_free(q->d_gh); dev_free(q->d_dvq); dev_free(q->d_vgpre);
+    dev_free(q->d_cov_v); dev_free(q->d_cov_s); dev_free(q->d_cov); dev_free(q->d_cov_tasks); dev_free(q->d_cov_pairs);
+    dev_free(q->d_cov_goff);
     dev_free(q->d_loo_x);               // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
@@ -373,7 +376,8 @@ int pmk_query_plan(pmk_query *q, double radius, double delta)
     }
     c->tic("plan");
     q->planned = false;
-    reset_item_state(q);
+    reset_plan_state(q);
+    q->explicit_items = false;
     q->total = 0;
     q->roff.assign((size_t)(m->P_global + 1), 0);
     if (q->Nq > 0) {
@@ -984,6 +988,207 @@ int pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weight
             if (!rc && dYq) rc = pmk_query_fetch_grad(q, dYq, lddy);
             return !rc && dVq ? pmk_query_fetch_vgrad(q, dVq, lddv) : rc;
         });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ joint covariance of the batch
+static const char COV_NEEDS_ALL[] = "the joint covariance needs a model that holds every leaf";
+
+// a kernel the covariance stages evaluate: any family, ModSqExp only at D = 1 (nothing here differentiates, so the
+// Brownian-bridge families are admitted)
+static int cov_kernel_ok(const pmk_kernel_desc *th, int D, const char *who, const char *role)
+{
+    if (!kernel_ok(th)) { set_error("%s: unknown kernel family (%s)", who, role); return -2; }
+    if (th->family == PMK_MODSQEXP && D > 1) {
+        set_error("%s: %s is PMK_MODSQEXP, which is defined for D = 1 only (D = %d)", who, role, D);
+        return -2;
+    }
+    return 0;
+}
+
+static int cov_batch_ok(int64_t Nq, const char *who)
+{
+    if (Nq > PMK_COV_MAX_QUERIES) {
+        set_error("%s: %lld queries, the Nq x Nq result is limited to PMK_COV_MAX_QUERIES = %d", who, (long long)Nq,
+                  PMK_COV_MAX_QUERIES);
+        return -5;
+    }
+    return 0;
+}
+
+// The strips of the covariance sweep, the pairs of strips of a region and the offsets of the region blocks, from the
+// plan's region offsets.  A region's items are dealt evenly over its strips, as build_strip_tasks (pmk_predict.hip)
+// deals them.  Returns the elements of the V arena.
+static int64_t cov_tasks_from_plan(pmk_query *q, std::vector<CovTask> &tasks, std::vector<CovPair> &pairs)
+{
+    const pmk_model *m = q->m;
+    int64_t voff = 0;
+    q->cov_goff.assign((size_t)m->P + 1, 0);
+    for (int64_t r = 0; r < m->P; ++r) {
+        const int64_t b = q->roff[(size_t)(m->leaf_base + r)], e = q->roff[(size_t)(m->leaf_base + r + 1)], mr = e - b;
+        q->cov_goff[(size_t)r + 1] = q->cov_goff[(size_t)r] + mr * mr;
+        if (mr == 0) continue;
+        const int64_t nstrips = (mr + TQ - 1) / TQ, w = (mr + nstrips - 1) / nstrips;
+        const size_t t0 = tasks.size();
+        for (int64_t f = b; f < e; f += w) {
+            CovTask t;
+            t.region = (int32_t)r;
+            t.count = (int32_t)std::min(e - f, w);
+            t.first = f;
+            t.voff = voff;
+            t.goff = q->cov_goff[(size_t)r];
+            t.m = (int32_t)mr;
+            t.a0 = (int32_t)(f - b);
+            tasks.push_back(t);
+            voff += (int64_t)m->desc[(size_t)r].ld * TQ;
+        }
+        for (size_t ta = t0; ta < tasks.size(); ++ta)
+            for (size_t tb = ta; tb < tasks.size(); ++tb) pairs.push_back({(int32_t)ta, (int32_t)tb});
+    }
+    return voff;
+}
+
+static int fetch_cov_common(pmk_query *q, double *Cov, int64_t ldc, hipMemcpyKind kind, const char *who)
+{
+    if (!q) { set_error("%s: query is NULL", who); return -1; }
+    if (!q->mixed_cov || !q->cov_items) { set_error("%s: pmk_query_mix_cov has not run on this plan", who); return -2; }
+    if (!Cov) { set_error("%s: Cov is NULL", who); return -2; }
+    if (ldc < q->Nq) { set_error("%s: ldc = %lld < Nq = %lld", who, (long long)ldc, (long long)q->Nq); return -4; }
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    if (q->Nq > 0)
+        PMK_HIP(hipMemcpy2DAsync(Cov, sizeof(double) * (size_t)ldc, q->d_cov, sizeof(double) * (size_t)q->Nq,
+                                 sizeof(double) * (size_t)q->Nq, (size_t)q->Nq, kind, c->stream));
+    return 0;
+}
+
+extern "C" {
+
+int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
+{
+    static const char who[] = "pmk_query_items_cov";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    pmk_model *m = q->m;
+    if (!m->fitted) { set_error("%s: the model holds no resident factor", who); return -1; }
+    if (int rc = whole_tree_ok(m, who, COV_NEEDS_ALL, -3)) return rc;
+    if (th) {
+        if (int rc = cov_kernel_ok(th, m->D, who, "theta")) return rc;
+    } else {
+        if (m->ths.empty()) { set_error("%s: the model holds no kernels (pmk_model_set_kernels)", who); return -3; }
+        for (size_t r = 0; r < m->ths.size(); ++r)
+            if (int rc = cov_kernel_ok(&m->ths[r], m->D, who, "the model's own theta")) return rc;
+        th = fitted_theta(m);
+    }
+    if (int rc = cov_batch_ok(q->Nq, who)) return rc;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    q->cov_items = q->mixed_cov = false;
+    std::vector<CovTask> tasks;
+    std::vector<CovPair> pairs;
+    const int64_t velems = cov_tasks_from_plan(q, tasks, pairs);
+    q->cov_ntasks = (int64_t)tasks.size();
+    q->cov_npairs = (int64_t)pairs.size();
+    if (int rc = grow_sized(q->d_cov_v, q->cov_v_cap, velems * (int64_t)m->esz, s, who, "the V arena")) return rc;
+    if (int rc = grow_sized(q->d_cov_s, q->cov_s_cap, q->cov_goff[(size_t)m->P], s, who, "the region blocks")) return rc;
+    if (int rc = grow_sized(q->d_cov_tasks, q->cov_tasks_cap, q->cov_ntasks, s, who, "the strip tasks")) return rc;
+    if (int rc = grow_sized(q->d_cov_pairs, q->cov_pairs_cap, q->cov_npairs, s, who, "the strip pairs")) return rc;
+    if (int rc = grow_sized(q->d_cov_goff, q->cov_goff_cap, m->P + 1, s, who, "the block offsets")) return rc;
+    PMK_HIP(hipMemcpyAsync(q->d_cov_goff, q->cov_goff.data(), sizeof(int64_t) * q->cov_goff.size(), hipMemcpyHostToDevice, s));
+    if (!tasks.empty()) {
+        PMK_HIP(hipMemcpyAsync(q->d_cov_tasks, tasks.data(), sizeof(CovTask) * tasks.size(), hipMemcpyHostToDevice, s));
+        PMK_HIP(hipMemcpyAsync(q->d_cov_pairs, pairs.data(), sizeof(CovPair) * pairs.size(), hipMemcpyHostToDevice, s));
+    }
+    PMK_HIP(hipStreamSynchronize(s));       // `tasks` and `pairs` are locals
+    c->tic("items_cov");
+    const int rc = PMK_BY_DTYPE(m, launch_items_cov(q, th, s));
+    c->toc("items_cov");
+    if (rc) return rc;
+    q->cov_items = true;
+    return 0;
+}
+
+int pmk_query_mix_cov(pmk_query *q, const pmk_kernel_desc *weight_th)
+{
+    static const char who[] = "pmk_query_mix_cov";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (q->explicit_items) {
+        set_error("%s: the query was made by pmk_query_create_items: its items belong to no blend", who);
+        return -2;
+    }
+    if (!q->cov_items) { set_error("%s: pmk_query_items_cov has not run on this plan", who); return -2; }
+    if (int rc = blend_profile_ok(weight_th, who)) return rc;
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    q->mixed_cov = false;
+    if (int rc = grow_sized(q->d_cov, q->cov_cap, q->Nq * q->Nq, c->stream, who, "the Nq x Nq result")) return rc;
+    c->tic("mix_cov");
+    const int rc = launch_mix_cov(q, *weight_th, c->stream);
+    c->toc("mix_cov");
+    if (rc) return rc;
+    q->mixed_cov = true;
+    return 0;
+}
+
+int pmk_query_fetch_cov(pmk_query *q, double *Cov, int64_t ldc)
+{
+    if (int rc = fetch_cov_common(q, Cov, ldc, hipMemcpyDeviceToHost, "pmk_query_fetch_cov")) return rc;
+    PMK_HIP(hipStreamSynchronize(q->m->ctx->stream));
+    return 0;
+}
+
+int pmk_query_fetch_cov_dev(pmk_query *q, double *Cov_dev, int64_t ldc)
+{
+    return fetch_cov_common(q, Cov_dev, ldc, hipMemcpyDeviceToDevice, "pmk_query_fetch_cov_dev");
+}
+
+int pmk_query_get_items_cov(pmk_query *q, int64_t region, int64_t *m_out, int32_t *query, double *S, int64_t lds)
+{
+    static const char who[] = "pmk_query_get_items_cov";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (!q->cov_items) { set_error("%s: pmk_query_items_cov has not run on this plan", who); return -2; }
+    const pmk_model *m = q->m;
+    if (region < m->leaf_base || region >= m->leaf_base + m->P) {
+        set_error("%s: region %lld is outside this model's leaves [%lld, %lld)", who, (long long)region,
+                  (long long)m->leaf_base, (long long)(m->leaf_base + m->P));
+        return -3;
+    }
+    const int64_t b = q->roff[(size_t)region], mr = q->roff[(size_t)region + 1] - b;
+    if (m_out) *m_out = mr;
+    if (S && lds < mr) { set_error("%s: lds = %lld < m = %lld", who, (long long)lds, (long long)mr); return -4; }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    if (mr == 0) return 0;
+    if (query) {
+        // the rows are the region's sorted items: ascending query index
+        std::vector<int32_t> item((size_t)mr), iq((size_t)q->total);
+        PMK_HIP(hipMemcpy(item.data(), q->d_sorted_item + b, sizeof(int32_t) * (size_t)mr, hipMemcpyDeviceToHost));
+        PMK_HIP(hipMemcpy(iq.data(), q->d_item_query, sizeof(int32_t) * (size_t)q->total, hipMemcpyDeviceToHost));
+        for (int64_t a = 0; a < mr; ++a) query[a] = iq[(size_t)item[(size_t)a]];
+    }
+    if (S)
+        PMK_HIP(hipMemcpy2D(S, sizeof(double) * (size_t)lds, q->d_cov_s + q->cov_goff[(size_t)(region - m->leaf_base)],
+                            sizeof(double) * (size_t)mr, sizeof(double) * (size_t)mr, (size_t)mr, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                   double radius, double delta, double *Yq, double *Vq, double *Cov, int64_t ldc)
+{
+    static const char who[] = "pmk_predict_mixture_cov_fitted";
+    if (!m) { set_error("%s: model is NULL", who); return -1; }
+    if (int rc = whole_tree_ok(m, who, COV_NEEDS_ALL, -3)) return rc;
+    if (Cov && ldc < Nq) { set_error("%s: ldc = %lld < Nq = %lld", who, (long long)ldc, (long long)Nq); return -4; }
+    if (Cov)
+        if (int rc = cov_batch_ok(Nq, who)) return rc;
+    // with Cov NULL no covariance stage runs
+    return one_shot(
+        m, Nq, Xq, radius, delta,
+        [&](pmk_query *q) { int rc = pmk_query_items_fitted(q); return !rc && Cov ? pmk_query_items_cov(q, nullptr) : rc; },
+        [&](pmk_query *q) { int rc = pmk_query_mix(q, weight_th, 0, Nq); return !rc && Cov ? pmk_query_mix_cov(q, weight_th) : rc; },
+        [&](pmk_query *q) { int rc = pmk_query_fetch(q, Yq, Vq); return !rc && Cov ? pmk_query_fetch_cov(q, Cov, ldc) : rc; });
 }
 
 }  // extern "C"

@@ -62,6 +62,16 @@ int grow(T *&p, int64_t &cap, int64_t need, hipStream_t s)
     return 0;
 }
 
+// grow() for a buffer whose size follows the caller's batch (the covariance arenas): a failed allocation says how many
+// bytes `what` asked for
+template <typename T>
+int grow_sized(T *&p, int64_t &cap, int64_t need, hipStream_t s, const char *who, const char *what)
+{
+    if (!grow(p, cap, need, s)) return 0;
+    set_error("%s: hipMalloc of %lld bytes for %s failed", who, (long long)(need * (int64_t)sizeof(T)), what);
+    return -100;
+}
+
 // One device allocation cut into 256-byte aligned pieces: a query object used to own two dozen small buffers, and every
 // hipFree is a device synchronisation (pmk_query_destroy: 3.4 ms of a 108 ms querymixtureGP! at config C).  add() names
 // a pointer and its element count, in the order of the pieces; commit() allocates and points every one of them into the
@@ -123,6 +133,12 @@ inline void reset_item_state(pmk_query *q)
     q->mixed_multi = false;
     q->items_fn = q->grad_items = q->mixed_grad = false;
     q->vgrad_items = q->mixed_vgrad = false;
+}
+// a new plan or new explicit items (not new item values: the covariance does not depend on them) discard the covariance
+inline void reset_plan_state(pmk_query *q)
+{
+    reset_item_state(q);
+    q->cov_items = q->mixed_cov = false;
 }
 
 // The one-shot calls: a query object for Xq, its plan, the three stages as the caller gives them, and the object goes

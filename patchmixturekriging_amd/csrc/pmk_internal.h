@@ -55,6 +55,20 @@ template <> struct HyperArgs<true> {
     using s2_t = const double *__restrict__;
 };
 
+// A strip of the covariance sweep (pmk_cov.hip): up to TQ sorted items of one region and their strip of the V arena.
+// Built on the host from the plan's region offsets (pmk_api_query.cpp), dealt over a region's strips as
+// build_strip_tasks deals them.
+struct CovTask {
+    int32_t region;   // local patch
+    int32_t count;    // items of the strip (<= TQ)
+    int64_t first;    // first sorted item of the strip
+    int64_t voff;     // element offset of the strip in the V arena: ld x TQ elements, leading dimension TQ
+    int64_t goff;     // element offset of the region's m x m block in the block buffer
+    int32_t m;        // items of the region
+    int32_t a0;       // position of `first` in the region's sorted segment
+};
+struct CovPair { int32_t ta, tb; };   // two strips of one region, ta <= tb
+
 // A BSP tree in heap order (root 0, children 2i+1 / 2i+2); leaves numbered left to right.
 struct BspArrays {
     int D = 0, levels = 0;
@@ -232,6 +246,17 @@ struct pmk_query {
     double *d_dvq = nullptr; int64_t dvq_cap = 0;     // Nq x D column-major: dVq[j + Nq d]
     int64_t *d_vgpre = nullptr; int64_t vgpre_cap = 0, vstrips = 0;   // strips of vgrad_strip_items(D) items per region: prefix [P+1]
     std::vector<int64_t> vgpre;         // host copy (source of the upload)
+    // joint covariance of the batch (pmk_cov.hip).  cov_items: pmk_query_items_cov has run on the current plan;
+    // mixed_cov: pmk_query_mix_cov after it.  A new plan or new items discard both.  All buffers grow only.
+    bool cov_items = false, mixed_cov = false;
+    bool explicit_items = false;        // the items are those of pmk_query_create_items: one per point, no blend
+    char *d_cov_v = nullptr; int64_t cov_v_cap = 0;               // V arena, bytes: one ld x TQ strip of the model's type per task
+    double *d_cov_s = nullptr; int64_t cov_s_cap = 0;             // region blocks, m_r x m_r column-major at cov_goff[r]
+    double *d_cov = nullptr; int64_t cov_cap = 0;                 // the result, Nq x Nq column-major
+    pmk::CovTask *d_cov_tasks = nullptr; int64_t cov_tasks_cap = 0, cov_ntasks = 0;
+    pmk::CovPair *d_cov_pairs = nullptr; int64_t cov_pairs_cap = 0, cov_npairs = 0;
+    int64_t *d_cov_goff = nullptr; int64_t cov_goff_cap = 0;      // P + 1
+    std::vector<int64_t> cov_goff;      // host copy: prefix of m_r^2
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -284,6 +309,7 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
     int launch_loo_member_multi(pmk_query *q, int noisy, int want_var, int32_t *d_mark, hipStream_t s);              \
     int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                   \
     int launch_items_vgrad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
+    int launch_items_cov(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                    \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)
@@ -307,6 +333,7 @@ int launch_trend_items(pmk_query *q, int R, int qt, bool want_var, hipStream_t s
 int launch_mix_grad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_trend_vgrad(pmk_query *q, hipStream_t s);
 int launch_mix_vgrad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
+int launch_mix_cov(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s);
 int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
                              const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);

@@ -39,6 +39,7 @@ static int no_gpu(const char *what)
     int launch_loo_member_multi(pmk_query *, int, int, int32_t *, hipStream_t) { return no_gpu("launch_loo_member_multi"); } \
     int launch_items_grad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_grad"); } \
     int launch_items_vgrad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_vgrad"); } \
+    int launch_items_cov(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_cov"); }  \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)
@@ -56,6 +57,7 @@ int launch_trend_items(pmk_query *, int, int, bool, hipStream_t) { return no_gpu
 int launch_mix_grad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_grad"); }
 int launch_trend_vgrad(pmk_query *, hipStream_t) { return no_gpu("launch_trend_vgrad"); }
 int launch_mix_vgrad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_vgrad"); }
+int launch_mix_cov(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_mix_cov"); }
 int launch_loo_scatter_multi(pmk_query *, const pmk_query *, int, int, const int32_t *, const int64_t *, hipStream_t)
 {
     return no_gpu("launch_loo_scatter_multi");

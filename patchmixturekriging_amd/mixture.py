@@ -805,6 +805,54 @@ class DeviceQuery:
         _lib.check(self.L.pmk_query_get_items_vgrad(self.h, _d(GV), D), "pmk_query_get_items_vgrad")
         return GV[:self.total]
 
+    # ---- joint covariance of the batch (pmk_cov.hip)
+    def items_cov(self, theta=None):
+        """pmk_query_items_cov: the posterior covariance block of every region over its items of this plan, with `theta`
+        for every patch or (None) the model's own kernels.  Single-output path: no trend, no targets needed.  Serves a
+        query made by from_items too.  Closure-carrying kernels raise TypeError before any device call."""
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            _refuse_closure_kernel(theta, "items_cov")
+            d = theta.desc()
+            ptr = C.byref(d)
+        _lib.check(self.L.pmk_query_items_cov(self.h, ptr), "pmk_query_items_cov")
+
+    def mix_cov(self, weight_theta):
+        """pmk_query_mix_cov: the joint covariance of the whole batch under the blend of mix()"""
+        _refuse_closure_kernel(weight_theta, "mix_cov")
+        d = weight_theta.desc()
+        _lib.check(self.L.pmk_query_mix_cov(self.h, C.byref(d)), "pmk_query_mix_cov")
+
+    def fetch_cov(self):
+        """Cov [Nq, Nq], symmetric: Cov[j, k] is the posterior covariance of the blended field at queries j and k"""
+        n = max(self.Nq, 1)
+        buf = np.empty((n, n))                      # Cov[j + ldc k]; symmetric, so the order does not matter
+        _lib.check(self.L.pmk_query_fetch_cov(self.h, _d(buf), n), "pmk_query_fetch_cov")
+        return buf[:self.Nq, :self.Nq]
+
+    def fetch_cov_into(self, Cov):
+        """pmk_query_fetch_cov_dev: Cov is a contiguous device array of shape (Nq, Nq) of float64 (a torch tensor):
+        device-to-device on the context's stream, no host synchronisation"""
+        ga = self._device_out(Cov, "Cov")
+        if ga.shape != (self.Nq, self.Nq) or (self.Nq > 0 and ga.strides != (self.Nq, 1)):
+            raise ValueError("Cov must be a C-contiguous device array of shape (%d, %d), not %s" % (self.Nq, self.Nq, ga.shape))
+        _lib.check(self.L.pmk_query_fetch_cov_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_cov_dev")
+
+    def item_covs(self, region):
+        """pmk_query_get_items_cov -> (query_idx [m], S [m, m]): the block of one global region; row a belongs to query
+        query_idx[a] (ascending)"""
+        m = C.c_int64()
+        _lib.check(self.L.pmk_query_get_items_cov(self.h, int(region), C.byref(m), None, None, 0), "pmk_query_get_items_cov")
+        n = max(m.value, 1)
+        idx = np.empty(n, dtype=np.int32)
+        S = np.empty((n, n))
+        _lib.check(self.L.pmk_query_get_items_cov(self.h, int(region), None, idx.ctypes.data_as(C.POINTER(C.c_int32)), _d(S), n),
+                   "pmk_query_get_items_cov")
+        return idx[:m.value], S[:m.value, :m.value]
+
     def debug(self):
         home = np.empty(self.Nq, dtype=np.int64)
         off = np.empty(self.Nq + 1, dtype=np.int64)
@@ -1293,6 +1341,68 @@ def querymixtureGP_patches(Xq, eta, root, levels, radius, delta, weight_theta, d
     q.mix(weight_theta)
     Yq, Vq = q.fetch()
     return Yq, Vq, (q.debug() if debug_flag else None)
+
+
+def _cov_query(Xq, eta, root, radius, delta, weight_theta, who):
+    """the planned query of the covariance front ends, with the means, variances and region blocks computed on the
+    model's own kernels.  Closure-carrying kernels (the blending profile, or the theta of the fit) raise TypeError before
+    any device call, as in the gradient front ends: their addends and warp features are functions of x the batch's joint
+    covariance would have to carry."""
+    _refuse_closure_kernel(weight_theta, who)
+    theta = getattr(getattr(eta, "_model", None), "theta", None)
+    if theta is not None:
+        _refuse_closure_kernel(theta, who)
+    q = _patches_query(Xq, eta, root, radius, delta, who)
+    q.items_fitted()
+    q.mix(weight_theta)
+    q.items_cov()
+    q.mix_cov(weight_theta)
+    return q
+
+
+def querymixtureGP_cov(Xq, eta, root, levels, radius, delta, weight_theta):
+    """querymixtureGP_patches with the joint posterior covariance of the batch under the blend -> (Yq, Vq, Cov [Nq, Nq]).
+    The patches are independent GPs: Cov[j, k] sums wn_j wn_k (k_r(x_j, x_k) - V_j . V_k) over the regions that hold an
+    item of both queries, and is exactly 0 where they share none; its diagonal is Vq up to rounding.  Single-output path,
+    no trend; at most 16384 queries."""
+    q = _cov_query(Xq, eta, root, radius, delta, weight_theta, "querymixtureGP_cov")
+    Yq, Vq = q.fetch()
+    return Yq, Vq, q.fetch_cov()
+
+
+def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None):
+    """posterior draws of the latent blended field at Xq -> (draws [n_draws, Nq] as a torch device tensor, jitter).
+    The joint covariance of querymixtureGP_cov is fetched into a device tensor and factored with
+    torch.linalg.cholesky_ex; if that fails, jitter * I is added, starting at 2^-52 trace / Nq and multiplied by 10 up to
+    2^-26 trace / Nq, after which LinAlgError is raised.  The jitter that was used is returned (0.0: none).  z
+    [n_draws, Nq]: the standard normals to use; otherwise they are drawn from `generator`.  draws = Yq + z L^T."""
+    import torch
+
+    q = _cov_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP")
+    dev = torch.device("cuda", q.model.ctx.device)
+    Nq = q.Nq
+    Cov = torch.empty((Nq, Nq), dtype=torch.float64, device=dev)
+    Yq = torch.empty(Nq, dtype=torch.float64, device=dev)
+    q.fetch_into(Yq)
+    q.fetch_cov_into(Cov)
+    q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
+    scale = float(torch.trace(Cov)) / max(Nq, 1)
+    jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
+    while True:
+        L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
+        if int(info) == 0:
+            break
+        jitter = 2.0 ** -52 * scale if jitter == 0.0 else 10.0 * jitter
+        if not jitter <= 2.0 ** -26 * scale:
+            raise np.linalg.LinAlgError("samplemixtureGP: the joint covariance is not positive definite with a jitter "
+                                        "of up to 2^-26 trace / Nq")
+    if z is None:
+        z = torch.randn((int(n_draws), Nq), dtype=torch.float64, device=dev, generator=generator)
+    else:
+        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
+        if tuple(z.shape) != (int(n_draws), Nq):
+            raise ValueError("z must have shape (%d, %d), not %s" % (int(n_draws), Nq, tuple(z.shape)))
+    return Yq[None, :] + z @ L.T, jitter
 
 
 def querymixtureGP_multi_patches(Xq, eta, root, levels, radius, delta, weight_theta, variance=True):
