@@ -21,7 +21,8 @@
 //
 // Bits.  Entry (a, b) of G_r is one chain of 16x16x4 MFMAs over the rows 0 .. ld - 1 in steps of four, whatever the
 // columns' places in their strips and whatever shares the tiles; the lower triangle is a copy of the upper one.  The
-// blend sums in the item order of j.  Nothing is accumulated across threads.
+// blend sums over the shared regions in ascending region index, whichever query comes first.  Nothing is accumulated
+// across threads.
 #include <algorithm>
 
 #include "pmk_dispatch.h"
@@ -291,9 +292,9 @@ int launch_items_cov(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s)
 constexpr int MIXC = 16;    // a workgroup blends a 16 x 16 tile of the result
 
 // Workgroup (bx, by), bx <= by, computes the entries (j, j') of the tile rows 16 bx .. and columns 16 by .. with j <= j'
-// and writes the tile and its mirror image, both with j along the lanes (the result is column-major).  For every item of
-// j, in the order of pmk_query_mix, the items of j' in the same region are looked for in their order (item lists are
-// short); an item's place in the region's sorted segment is item_pos - roff[region].  The neighbour search can accept one
+// and writes the tile and its mirror image, both with j along the lanes (the result is column-major).  For every region
+// of j, in ascending region index, the items of j and of j' in that region are looked for in their order (item lists
+// are short); an item's place in the region's sorted segment is item_pos - roff[region].  The neighbour search can accept one
 // leaf through two hyperplanes, so a query may hold two items of a region: every pair of items of the two queries that
 // share a region is a term, which is the covariance of the two blends as they are.  A query that blends an item of a
 // failed patch is NaN in its whole row and column, also where the two queries share no region; other entries without a
@@ -317,18 +318,46 @@ __global__ __launch_bounds__(MIXC *MIXC) void mix_cov_kernel(int64_t Nq, const i
         const double sw = blend_weight_sum(wth, item_t, b, e), swp = blend_weight_sum(wth, item_t, bp, ep);
         bool bad = false;
         for (int64_t it = bp; it < ep; ++it) bad = bad || patch_is_bad(info, nullptr, item_region[it]);
-        bool first = true;
+        // one term: the pair (it, ip) of items of j and j' in region r, added to the chain a (n: terms before it)
+        auto add_term = [&](int64_t it, int64_t ip, int32_t r, double a, int n) {
+            const double wn = blend_weight(wth, item_t, it, e) / sw, wnp = blend_weight(wth, item_t, ip, ep) / swp;
+            const int64_t m = roff[r + 1] - roff[r];
+            const double s = S[goff[r] + (item_pos[it] - roff[r]) + m * (item_pos[ip] - roff[r])];
+            return n == 0 ? (wn * wnp) * s : __builtin_fma(wn * wnp, s, a);
+        };
+        // The sum of an entry is a chain of fused multiply-adds over its terms in ASCENDING region index, so that it does
+        // not depend on which of its two queries has the lower index: two queries at one point have equal rows, and a
+        // sub-batch in any order keeps the bits of its entries.  The items of j are walked in their own order first;
+        // nearly every entry has at most one term or meets its regions in ascending order, and is done.
+        int nterm = 0;
+        int32_t last = -1;
+        bool ascending = true;
         for (int64_t it = b; it < e; ++it) {
             const int32_t r = item_region[it];
             bad = bad || patch_is_bad(info, nullptr, r);
             for (int64_t ip = bp; ip < ep; ++ip) {
                 if (item_region[ip] != r) continue;
-                const double wn = blend_weight(wth, item_t, it, e) / sw, wnp = blend_weight(wth, item_t, ip, ep) / swp;
-                const int64_t m = roff[r + 1] - roff[r];
-                const double s = S[goff[r] + (item_pos[it] - roff[r]) + m * (item_pos[ip] - roff[r])];
-                const double term = (wn * wnp) * s;
-                acc = first ? term : acc + term;
-                first = false;
+                acc = add_term(it, ip, r, acc, nterm);
+                ++nterm;
+                ascending = ascending && r >= last;
+                last = r;
+            }
+        }
+        if (nterm >= 2 && !ascending) {
+            nterm = 0;
+            for (int32_t prev = -1;;) {
+                int32_t r = INT32_MAX;
+                for (int64_t it = b; it < e; ++it) {
+                    const int32_t rr = item_region[it];
+                    if (rr > prev && rr < r) r = rr;
+                }
+                if (r == INT32_MAX) break;
+                prev = r;
+                for (int64_t it = b; it < e; ++it) {
+                    if (item_region[it] != r) continue;
+                    for (int64_t ip = bp; ip < ep; ++ip)
+                        if (item_region[ip] == r) acc = add_term(it, ip, r, acc, nterm++);
+                }
             }
         }
         if (bad) acc = __builtin_nan("");

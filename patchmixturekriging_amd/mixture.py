@@ -1374,7 +1374,8 @@ def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws,
     """posterior draws of the latent blended field at Xq -> (draws [n_draws, Nq] as a torch device tensor, jitter).
     The joint covariance of querymixtureGP_cov is fetched into a device tensor and factored with
     torch.linalg.cholesky_ex; if that fails, jitter * I is added, starting at 2^-52 trace / Nq and multiplied by 10 up to
-    2^-26 trace / Nq, after which LinAlgError is raised.  The jitter that was used is returned (0.0: none).  z
+    2^-26 trace / Nq, after which LinAlgError is raised.  A batch that blends a patch whose factorisation failed has NaN
+    in its covariance and raises LinAlgError before any factorisation.  The jitter that was used is returned (0.0: none).  z
     [n_draws, Nq]: the standard normals to use; otherwise they are drawn from `generator`.  draws = Yq + z L^T."""
     import torch
 
@@ -1386,7 +1387,12 @@ def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws,
     q.fetch_into(Yq)
     q.fetch_cov_into(Cov)
     q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
-    scale = float(torch.trace(Cov)) / max(Nq, 1)
+    if not bool(torch.isfinite(Cov).all()):
+        # a query that blends a patch whose factorisation failed is NaN in its row and column; cholesky_ex need not
+        # report a NaN through info, and the draws would be NaN with jitter == 0.0
+        raise np.linalg.LinAlgError("samplemixtureGP: the joint covariance holds NaN or Inf entries: a query of the batch "
+                                    "blends a patch whose factorisation failed (DeviceModel.info())")
+    scale =float(torch.trace(Cov)) / max(Nq, 1)
     jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
     while True:
         L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
