@@ -615,6 +615,45 @@ int  pmk_query_get_items_cov(pmk_query *q, int64_t region, int64_t *m, int32_t *
 int  pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                     double radius, double delta, double *Yq, double *Vq, double *Cov, int64_t ldc);
 
+/* ---- appending observations to a fitted model in place: the border of the Cholesky factor ---------------------------
+ * A patch's buffers are laid out for ld_r = 128 ceil(n_r / 128) rows, so up to ld_r - n_r new points fit without moving
+ * anything.  For the m new points Xn of a patch with resident factor L:
+ *   L' = [ L 0 ; L21 L22 ],  L21^T = V = L^-1 k_r(X, Xn),  L22 L22^T = k_r(Xn, Xn) + sigma2_r I (+ addends) - V^T V,
+ *   z' = [ z ; L22^-1 (yn - L21 z) ],  c' = L'^-T z',
+ * with the patch's own theta_r and sigma2_r.  V and V^T V come from the covariance sweep of pmk_query_items_cov (its
+ * kernels as they are, no variance floor on the diagonal), the border from one workgroup per receiving patch, c from the
+ * back substitution of the fit, run over every patch (one launch whatever received points; the split path has no other
+ * form).  Rows and columns < n_r of L, z and the -D^-1 blocks that do not meet the new rows keep their bits; c changes in
+ * every row.  Both precisions; works on a model on the split path.  Memory, owned by the model, grow only, freed with it:
+ * one ld_r x 256 strip of the model's type per receiving patch, 8 sum m_r^2 bytes of blocks and the staged items; a failed
+ * allocation returns -100 with the bytes asked for in the text.  Stage timers "append_sweep", "append_border" and
+ * "append_solve".
+ * Out of scope: growing a patch past ld_r (no reallocation), removing points, device-resident x / y arguments, the
+ * sharded exchanges, and the leaf lists of the tree itself (pmk_bsp_arrays still describes the points it was built on). */
+/* free_rows[P]: ld_r - n_r, the points patch r can still take */
+int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
+/* n_items items (point, target, patch): x host, point-major n_items x D; y host; diag host addends of the kernel's
+ * diagonal, or NULL (zeros; -2 if given for a model without pmk_model_set_diag addends); patch[i] the local patch of
+ * item i.  The items of one patch become its rows n_r, n_r + 1, ... in the order given; a point of several patches is
+ * several items.  global_index[i], the global point of item i, is required on a model of pmk_model_create_from_bsp and
+ * must be NULL otherwise; it is at least the model's N (a new observation is a new global point) and occurs once per
+ * patch: N grows to 1 + the largest index, the index list is rebuilt (one host round trip), and the
+ * *_global setters then expect the new N.  Blocks while the items are staged, then enqueues.
+ * A pivot of L22 that is <= 0 or NaN at new row a sets info[r] = n_r + a + 1 (the leading-minor convention of the fit);
+ * the patch is then failed as after a failed fit, until the next fit, and no other patch is touched by it.  A patch that
+ * had failed before takes its points, targets and n and stays failed.
+ * After the call: leave-one-out values are stale (pmk_model_loo again), the multi-output targets and the trend state are
+ * discarded (pmk_model_set_targets_multi again, with n_r + m_r rows, before pmk_model_solve_multi).  The geometry (nt, ld,
+ * offsets, schedule, split mode) is unchanged.  Query objects created earlier keep their plan; their item, gradient and
+ * covariance results are stale and nothing tracks that: run the item stages again.
+ * Refused before any device work, nothing changed: -1 model NULL, not fitted, or built by pmk_model_load (it holds no
+ * targets); -2 NULL arrays, global_index given or missing against the model's kind, diag without addends in the model;
+ * -3 a patch index out of range, a global index below N or beyond 2^31-3, or one given twice for a patch; -4 a patch's
+ * capacity exceeded (the text names the patch, its free rows and the rows asked for); -5 more than PMK_COV_MAX_QUERIES items; -6 a non-finite coordinate, target or addend.
+ * n_items = 0 returns 0 and touches nothing. */
+int  pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const double *y, const double *diag,
+                      const int32_t *patch, const int64_t *global_index);
+
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,
                     const double *c, int64_t Nq, const double *Xq, double *Yq);

@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, appendmixtureGP!, capacitymixtureGP
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -529,6 +529,66 @@ function fitmixtureGP!(Î·::MixtureGPType{T}, y_parts::Vector{Vector{T}}, Î¸, ÏƒÂ
             Î·.L_set[r]; Î·.U_set[r]                                  # pulled and cached
         end
     end
+    return Î·
+end
+
+"""capacitymixtureGP(Î·) -> the points every patch can still take in place: ld_r - n_r, ld_r = 128 ceil(n_r / 128)."""
+function capacitymixtureGP(Î·::MixtureGPType)
+    Î·.model == C_NULL && throw(PMKError("fitmixtureGP! must run before capacitymixtureGP"))
+    free = Vector{Int64}(undef, length(Î·.X_parts))
+    check(ccall((:pmk_model_capacity, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}), Î·.model, free), "pmk_model_capacity")
+    return free
+end
+
+"""appendmixtureGP!(Î·, X_new_parts, y_new_parts; global_index_parts) -> Î·: the new points X_new_parts[r] (empty entries
+allowed) with targets y_new_parts[r] become the last rows of patch r of the fitted Î·, in place: the resident Cholesky
+factor is bordered, not refitted (pmk_model_append).  On an Î· built by MixtureGPType(root, X, Îµ) the global index of every
+new row is required (global_index_parts[r], 0-based; a point of several patches is a row in each).  c_set, L_set and U_set
+follow; a failed new pivot throws PosDefException and leaves that patch failed until the next fit.  Kernels that carry a
+closure are not served: their points carry more than the positions."""
+function appendmixtureGP!(Î·::MixtureGPType{T}, X_new_parts::Vector{Vector{Vector{T}}}, y_new_parts::Vector{Vector{T}};
+                          global_index_parts::Union{Nothing,Vector{Vector{Int}}} = nothing) where T
+    Î·.model == C_NULL && throw(PMKError("fitmixtureGP! must run before appendmixtureGP!"))
+    P = length(Î·.X_parts)
+    length(X_new_parts) == P && length(y_new_parts) == P || throw(ArgumentError("one list of new points and targets per patch"))
+    (Î·.N_global > 0) == (global_index_parts !== nothing) ||
+        throw(ArgumentError("global_index_parts is required on an Î· built from a tree, and only there"))
+    free = capacitymixtureGP(Î·)
+    D = length(Î·.X_parts[1][1])
+    x = Float64[]; y = Float64[]; patch = Int32[]; g = Int64[]
+    for r = 1:P
+        m = length(X_new_parts[r])
+        length(y_new_parts[r]) == m || throw(ArgumentError("patch $r: $(length(y_new_parts[r])) targets for $m new points"))
+        m <= free[r] || throw(ArgumentError("patch $r has $(free[r]) free rows, $m rows asked for"))
+        for a = 1:m
+            length(X_new_parts[r][a]) == D || throw(ArgumentError("patch $r: a new point of dimension $(length(X_new_parts[r][a])), not $D"))
+            append!(x, X_new_parts[r][a]); push!(y, y_new_parts[r][a]); push!(patch, r - 1)
+            global_index_parts === nothing || push!(g, global_index_parts[r][a])
+        end
+    end
+    isempty(y) && return Î·
+    all(isfinite, x) && all(isfinite, y) || throw(ArgumentError("non-finite coordinate or target"))
+    check(ccall((:pmk_model_append, libpmk), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}),
+        Î·.model, length(y), x, y, C_NULL, patch, global_index_parts === nothing ? C_NULL : g), "pmk_model_append")
+    for r = 1:P
+        append!(Î·.X_parts[r], X_new_parts[r])
+    end
+    Î·.N_global > 0 && (Î·.N_global = max(Î·.N_global, maximum(g) + 1))
+    Î·.R_multi = 0
+    n = Int[length(X) for X in Î·.X_parts]
+    empty!(Î·.U_set.cache); empty!(Î·.L_set.cache)
+    Î·.U_set.n = n; Î·.L_set.n = n
+    info = Vector{Int32}(undef, P)
+    check(ccall((:pmk_model_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), Î·.model, info), "pmk_model_info")
+    cs = [Vector{Float64}(undef, n[r]) for r = 1:P]
+    GC.@preserve cs check(ccall((:pmk_model_get_weights, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), Î·.model,
+                                [pointer(c) for c in cs]), "pmk_model_get_weights")
+    for r = 1:P
+        Î·.c_set[r] = cs[r]
+    end
+    bad = findfirst(!=(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
     return Î·
 end
 

@@ -1,5 +1,6 @@
-// Host-side helpers shared by the sources of the C ABI (pmk_api.cpp, pmk_api_query.cpp, pmk_api_loo_mix.cpp): device
-// allocations, the checks and the drivers that more than one of them needs.  Host code only: no .hip file includes this.
+// Host-side helpers shared by the sources of the C ABI (pmk_api.cpp, pmk_api_query.cpp, pmk_api_loo_mix.cpp,
+// pmk_api_append.cpp): device allocations, the checks and the drivers that more than one of them needs.  Host code only:
+// no .hip file includes this.
 #pragma once
 
 #include <vector>
@@ -125,6 +126,9 @@ inline int whole_tree_ok(const pmk_model *m, const char *who, const char *tail, 
 
 // q->mcpre and q->mchunks from the region offsets of q's plan (pmk_api.cpp)
 void multi_chunk_prefix(pmk_query *q);
+
+// the buffers of pmk_model_append go with the model (pmk_api_append.cpp; called by pmk_model_destroy)
+void append_release(pmk_model *m);
 
 // a new plan or new items discard what the multi-output and gradient stages left on the query
 inline void reset_item_state(pmk_query *q)

@@ -191,6 +191,13 @@ struct pmk_model {
     int32_t *d_gchunk = nullptr;        // P + 1: prefix over ceil(ld_r / 256)
     int64_t gchunks = 0;
     double *d_gstage = nullptr; size_t gstage_bytes = 0;   // device copy of a host array handed to a *_global setter (grow only)
+    // pmk_model_append (pmk_api_append.cpp, pmk_append.hip).  append_q is no query of the ABI: it carries the arguments
+    // of launch_items_cov (tasks, pairs, V arena, blocks, points, addends, no variance floor) for the appended items,
+    // grouped by patch, with the identity as item order (d_app_iota).  All buffers grow only and go with the model.
+    pmk_query *append_q = nullptr;
+    double *d_app_y = nullptr, *d_app_diag = nullptr;      // targets and addends of the staged items
+    int32_t *d_app_iota = nullptr;
+    int64_t app_x_cap = 0, app_qdiag_cap = 0, app_y_cap = 0, app_diag_cap = 0, app_iota_cap = 0;
 };
 
 struct pmk_query {
@@ -310,6 +317,8 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
     int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                   \
     int launch_items_vgrad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
     int launch_items_cov(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                    \
+    int launch_append_border(pmk_model *m, const pmk_query *q, const double *d_y, const double *d_diag, hipStream_t s); \
+    int set_append_attributes();                                                                                     \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)

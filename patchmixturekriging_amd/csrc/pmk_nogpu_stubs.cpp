@@ -40,6 +40,8 @@ static int no_gpu(const char *what)
     int launch_items_grad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_grad"); } \
     int launch_items_vgrad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_vgrad"); } \
     int launch_items_cov(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_cov"); }  \
+    int launch_append_border(pmk_model *, const pmk_query *, const double *, const double *, hipStream_t) { return no_gpu("launch_append_border"); } \
+    int set_append_attributes() { return 0; }                                                                       \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .context import default_context
 from .kernels import as_points
-from .partition import _native, hyperplane_arrays
+from .partition import _native, findpartition, hyperplane_arrays
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -181,6 +181,7 @@ class DeviceModel:
         self.dtype, self.D, self.N = dtype, xa.shape[1], N
         self._from_tree, self._X, self._X_global = True, None, (None if xa.device else X)
         self.leaf_base = int(leaf_base)
+        self._root, self._eps = root, (None if eps is None else float(eps))     # append_global assigns with them
         self.P = int(L.pmk_model_num_patches(h))
         self._all_leaves = self.leaf_base == 0 and self.P == int(L.pmk_bsp_num_leaves(nat.h))
         self._index = None
@@ -464,6 +465,80 @@ class DeviceModel:
     def set_bsp(self, root, leaf_base=0):
         _lib.check(self.ctx.L.pmk_model_set_bsp(self.h, _native(root).h, int(leaf_base)), "pmk_model_set_bsp")
         self.leaf_base = int(leaf_base)
+
+    # ---- appending observations to the resident factor in place: the border of the Cholesky factor (include/pmk.h)
+    def capacity(self):
+        """pmk_model_capacity -> int64 [P]: the points every patch can still take, ld_r - n_r with ld_r = 128 ceil(n_r / 128)"""
+        free = np.empty(self.P, dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_capacity(self.h, _i(free)), "pmk_model_capacity")
+        return free
+
+    def _need_appendable(self, who):
+        self._need()
+        if not self._has_targets:
+            raise _lib.PmkError("%s: a model built from factors holds no targets: z cannot be extended" % who)
+
+    def _append(self, x, y, diag, patch, gidx):
+        _lib.check(self.ctx.L.pmk_model_append(self.h, len(y), _d(x), _d(y), None if diag is None else _d(diag),
+                                               patch.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               None if gidx is None else _i(gidx)), "pmk_model_append")
+        self.n = self.n + np.bincount(patch, minlength=self.P).astype(np.int64)
+        self._loo_done = self._multi_solved = False
+        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+
+    def append(self, X_new_parts, y_new_parts, diag_parts=None):
+        """pmk_model_append: X_new_parts[r] (m_r x D, m_r = 0 allowed) become the rows n_r .. n_r + m_r - 1 of patch r, with
+        targets y_new_parts[r] and, on a model with set_diag addends, diag_parts[r] (None: zeros) -> info.  L, z and c of the
+        resident factor are extended in place (no refit); loo() and the multi-output targets have to be set again."""
+        self._need_appendable("append")
+        if getattr(self, "_from_tree", False):
+            raise _lib.PmkError("append: a model built by from_tree takes append_global")
+        x, y, diag, patch, parts = append_items(X_new_parts, y_new_parts, diag_parts, self.n, self.D)
+        if len(y):
+            self._append(x, y, diag, patch, None)
+            self.X = [np.ascontiguousarray(np.vstack([a, b])) for a, b in zip(self.X, parts)]
+        return self.info()
+
+    def append_global(self, X_new, y_new):
+        """pmk_model_append on a model built by from_tree: the points X_new (m x D) with targets y_new get the global
+        indices N, N + 1, ... and go to the patches the tree assigns them at the eps of from_tree (pmk_bsp_assign; eps=None:
+        the home leaf only) -> (first_global_index, n_items).  A point of several eps-sets is one item in each.  The tree's
+        own leaf lists are not updated."""
+        self._need_tree_model("append_global")
+        self._need_appendable("append_global")
+        if not self._all_leaves:
+            raise _lib.PmkError("append_global: the model holds a shard of the tree's leaves")
+        Xn = as_points(X_new)
+        yn = np.ascontiguousarray(y_new, dtype=np.float64).reshape(-1)
+        if Xn.shape[1] != self.D:
+            raise ValueError("X_new must have shape (m, %d), not %s" % (self.D, Xn.shape))
+        if len(yn) != Xn.shape[0]:
+            raise ValueError("one target per new point: %d targets for %d points" % (len(yn), Xn.shape[0]))
+        if not (np.all(np.isfinite(Xn)) and np.all(np.isfinite(yn))):
+            raise ValueError("non-finite coordinate or target")
+        first, m = int(self.N), Xn.shape[0]
+        if m == 0:
+            return first, 0
+        L, h = self.ctx.L, _native(self._root).h
+        if self._eps is None:
+            point = np.arange(m, dtype=np.int64)
+            patch = np.array([findpartition(Xn[i], self._root) for i in range(m)], dtype=np.int64)     # raises on an error code
+        else:
+            off = np.empty(self.P + 1, dtype=np.int64)
+            _lib.check(L.pmk_bsp_assign(h, m, _d(Xn), self._eps, _i(off), None, None, None), "pmk_bsp_assign")
+            inds, loff = np.empty(max(int(off[-1]), 1), dtype=np.int64), np.empty(m + 1, dtype=np.int64)
+            lists = np.empty(max(int(off[-1]), 1), dtype=np.int64)
+            _lib.check(L.pmk_bsp_assign(h, m, _d(Xn), self._eps, _i(off), _i(inds), _i(loff), _i(lists)), "pmk_bsp_assign")
+            point = np.repeat(np.arange(m, dtype=np.int64), np.diff(loff))     # point-major: ascending within a patch
+            patch = lists[:int(loff[-1])].copy()
+        check_append_counts(np.bincount(patch, minlength=self.P), self.n)
+        self._append(np.ascontiguousarray(Xn[point]), np.ascontiguousarray(yn[point]), None, patch.astype(np.int32),
+                     np.ascontiguousarray(first + point))
+        self.N = first + m
+        self._index = self._X = None        # read back / cut again on first use
+        if self._X_global is not None:
+            self._X_global = np.ascontiguousarray(np.vstack([self._X_global, Xn]))
+        return first, len(point)
 
 
 class DeviceQuery:
@@ -958,6 +1033,58 @@ def patch_hyper(thetas, sigma2s, P):
     return descs, s2
 
 
+MAX_APPEND_ITEMS = 16384     # PMK_COV_MAX_QUERIES: the appended items run through the covariance sweep
+
+
+def check_append_counts(counts, n):
+    """the rows asked for against the free rows ld_r - n_r of every patch, ld_r = 128 ceil(n_r / 128), and the items of
+    one call against MAX_APPEND_ITEMS (ValueError before any device call)"""
+    for r, (m, nr) in enumerate(zip(counts, n)):
+        free = 128 * ((int(nr) + 127) // 128) - int(nr)
+        if m > free:
+            raise ValueError("patch %d has %d free rows (n = %d), %d rows asked for" % (r, free, int(nr), int(m)))
+    if int(np.sum(counts)) > MAX_APPEND_ITEMS:
+        raise ValueError("%d items in one call, the limit is %d" % (int(np.sum(counts)), MAX_APPEND_ITEMS))
+
+
+def append_items(X_new_parts, y_new_parts, diag_parts, n, D):
+    """validate the lists of DeviceModel.append against the patch sizes n and the dimension D -> (x [T, D], y [T],
+    diag [T] or None, patch int32 [T], parts): the items grouped by patch, and the new points of every patch as (m_r, D)
+    arrays.  ValueError for a wrong length, shape, a non-finite value or a full patch, before any device call."""
+    P = len(n)
+    parts, ys = list(X_new_parts), list(y_new_parts)
+    ds = None if diag_parts is None else list(diag_parts)
+    for what, lst in (("array of new points", parts), ("vector of new targets", ys), ("vector of addends", ds)):
+        if lst is not None and len(lst) != P:
+            raise ValueError("one %s per patch: got %d for %d patches" % (what, len(lst), P))
+    out_x, out_y, out_d = [], [], []
+    for r in range(P):
+        x = np.asarray(parts[r], dtype=np.float64)
+        if x.size == 0:
+            x = x.reshape(0, D)
+        elif x.ndim == 1:
+            x = x.reshape(-1, D) if D == 1 else x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[1] != D:
+            raise ValueError("patch %d: new points must have shape (m, %d), not %s" % (r, D, x.shape))
+        y = np.asarray(ys[r], dtype=np.float64).reshape(-1)
+        if len(y) != x.shape[0]:
+            raise ValueError("patch %d: %d targets for %d new points" % (r, len(y), x.shape[0]))
+        d = np.zeros(len(y)) if ds is None or ds[r] is None else np.asarray(ds[r], dtype=np.float64).reshape(-1)
+        if len(d) != len(y):
+            raise ValueError("patch %d: %d addends for %d new points" % (r, len(d), len(y)))
+        if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y)) and np.all(np.isfinite(d))):
+            raise ValueError("patch %d: non-finite coordinate, target or addend" % r)
+        out_x.append(np.ascontiguousarray(x))
+        out_y.append(y)
+        out_d.append(d)
+    counts = np.array([len(y) for y in out_y], dtype=np.int64)
+    check_append_counts(counts, n)
+    patch = np.repeat(np.arange(P, dtype=np.int32), counts)
+    x = np.ascontiguousarray(np.vstack(out_x)) if P else np.zeros((0, D))
+    diag = None if ds is None else np.ascontiguousarray(np.concatenate(out_d))
+    return x, np.ascontiguousarray(np.concatenate(out_y)), diag, patch, out_x
+
+
 def fit_patches(X_parts, y_parts, theta, sigma2, ctx=None, dtype="f64"):
     """create + fit + info + weights: the batched path behind fitmixtureGP! and fitRKHS!.  X_parts are POSITIONS: for a
     warp-feature kernel the model is built on the augmented points, and a DPP kernel's point-dependent diagonal term goes
@@ -1062,6 +1189,29 @@ def fitmixtureGP_(eta, y_parts, theta, sigma2):
     model, cs, info = fit_patches(eta.X_parts, y_parts, theta, sigma2)
     _raise_if_failed(info)
     _store_fit(eta, model, cs, [sigma2] * len(cs))
+    return eta
+
+
+def appendmixtureGP_(eta, X_new_parts, y_new_parts):
+    """condition the fitted eta on new observations in place -> eta.  X_new_parts[r], y_new_parts[r] are the new points
+    and targets of patch r (empty entries allowed); on an eta built by MixtureGPType.from_tree they are ONE array of new
+    points and their targets, assigned to the patches by the tree (DeviceModel.append_global).  The resident factor is
+    bordered, not refitted; c_set, L_set and U_set follow.  Raises PosDefException(patch, k) like fitmixtureGP_ when a
+    new pivot fails: that patch is then failed as after a failed fit until the next fit (its scores, gradient, covariance
+    and leave-one-out items are NaN; the plain item means and variances carry no mark, as after a failed fit), the others
+    are conditioned as asked."""
+    model = _fitted_model(eta, "appendmixtureGP_")
+    if getattr(model, "theta", None) is not None:
+        _refuse_closure_kernel(model.theta, "appendmixtureGP_")
+    if getattr(eta, "_from_tree", False):
+        model.append_global(X_new_parts, y_new_parts)
+        info = model.info()
+    else:
+        info = model.append(X_new_parts, y_new_parts)
+        eta.X_parts = model.X
+    _store_fit(eta, model, model.weights(), eta.sigma2_set)
+    eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the append: fit those again
+    _raise_if_failed(info)
     return eta
 
 
