@@ -636,8 +636,9 @@ int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
  * diagonal, or NULL (zeros; -2 if given for a model without pmk_model_set_diag addends); patch[i] the local patch of
  * item i.  The items of one patch become its rows n_r, n_r + 1, ... in the order given; a point of several patches is
  * several items.  global_index[i], the global point of item i, is required on a model of pmk_model_create_from_bsp and
- * must be NULL otherwise; it is at least the model's N (a new observation is a new global point) and occurs once per
- * patch: N grows to 1 + the largest index, the index list is rebuilt (one host round trip), and the
+ * must be NULL otherwise; it is at least the model's N (a new observation is a new global point), occurs once per
+ * patch, and the indices of one patch strictly ascend in the order given (the rows follow that order and a patch's index
+ * list is searched by bisection, so the call does not sort: it refuses): N grows to 1 + the largest index, the index list is rebuilt (one host round trip), and the
  * *_global setters then expect the new N.  Blocks while the items are staged, then enqueues.
  * A pivot of L22 that is <= 0 or NaN at new row a sets info[r] = n_r + a + 1 (the leading-minor convention of the fit);
  * the patch is then failed as after a failed fit, until the next fit, and no other patch is touched by it.  A patch that
@@ -648,7 +649,8 @@ int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
  * covariance results are stale and nothing tracks that: run the item stages again.
  * Refused before any device work, nothing changed: -1 model NULL, not fitted, or built by pmk_model_load (it holds no
  * targets); -2 NULL arrays, global_index given or missing against the model's kind, diag without addends in the model;
- * -3 a patch index out of range, a global index below N or beyond 2^31-3, or one given twice for a patch; -4 a patch's
+ * -3 a patch index out of range, a global index below N or beyond 2^31-3, one given twice for a patch, or the indices of a patch
+ * not ascending in the order given (the text names the patch and the index); -4 a patch's
  * capacity exceeded (the text names the patch, its free rows and the rows asked for); -5 more than PMK_COV_MAX_QUERIES items; -6 a non-finite coordinate, target or addend.
  * n_items = 0 returns 0 and touches nothing. */
 int  pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const double *y, const double *diag,

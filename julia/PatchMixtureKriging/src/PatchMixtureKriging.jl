@@ -543,7 +543,8 @@ end
 """appendmixtureGP!(η, X_new_parts, y_new_parts; global_index_parts) -> η: the new points X_new_parts[r] (empty entries
 allowed) with targets y_new_parts[r] become the last rows of patch r of the fitted η, in place: the resident Cholesky
 factor is bordered, not refitted (pmk_model_append).  On an η built by MixtureGPType(root, X, ε) the global index of every
-new row is required (global_index_parts[r], 0-based; a point of several patches is a row in each).  c_set, L_set and U_set
+new row is required (global_index_parts[r], 0-based, at least the old N and strictly ascending within a patch: the rows
+follow the order given, and an order that does not ascend is refused; a point of several patches is a row in each).  c_set, L_set and U_set
 follow; a failed new pivot throws PosDefException and leaves that patch failed until the next fit.  Kernels that carry a
 closure are not served: their points carry more than the positions."""
 function appendmixtureGP!(η::MixtureGPType{T}, X_new_parts::Vector{Vector{Vector{T}}}, y_new_parts::Vector{Vector{T}};

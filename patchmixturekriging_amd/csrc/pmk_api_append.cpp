@@ -148,6 +148,19 @@ int pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const doubl
             set_error("%s: global index %lld is given twice for patch %d", who, (long long)dup->second, (int)dup->first);
             return -3;
         }
+        // a patch's index list stays ascending (patch_holds of pmk_items.h searches it by bisection), and the rows follow
+        // the order given: so that order has to ascend.  The first new index of a patch is >= N, above its old entries
+        std::vector<int64_t> last((size_t)P, -1);
+        for (int64_t i = 0; i < n_items; ++i) {
+            int64_t &prev = last[(size_t)patch[i]];
+            if (global_index[i] < prev) {
+                set_error("%s: item %lld gives patch %d the global index %lld after %lld: the global indices of a patch must "
+                          "ascend in the order given", who, (long long)i, (int)patch[i], (long long)global_index[i],
+                          (long long)prev);
+                return -3;
+            }
+            prev = global_index[i];
+        }
     }
     for (int64_t i = 0; i < n_items; ++i) {
         bool finite = std::isfinite(y[i]) && (!diag || std::isfinite(diag[i]));

@@ -34,6 +34,17 @@ MIXED_SIZES = [(30, 5), (96, 32), (129, 2), (40, 0), (127, 1)]
 MIXED_NAMES = ["spline34", "gaussian", "rq", "spline12", "rq"]
 MIXED_SIGMA2 = {"f64": [1e-2, 2e-2, 5e-2, 1e-2, 3e-2], "f32": [0.05, 0.08, 0.1, 0.05, 0.06]}
 THREE_SIZES = [(30, 3), (125, 3), (300, 3)]
+# the border kernel walks a column of width cw = the power of two >= max(m, 16): m on both sides of 16, 32 (MAIN_SIZES has
+# m = 32) and 64, and cw = 64 (four row groups) on one, two, three and five block rows
+WIDTH_SIZES = [(100, 16), (100, 17), (60, 33), (64, 64), (63, 65), (200, 56), (300, 48), (513, 40)]
+
+
+def column_width(m):
+    """cw of append_border_kernel for m new rows"""
+    cw = 16
+    while cw < m:
+        cw *= 2
+    return cw
 
 
 def rnd(a, dtype):
@@ -98,6 +109,10 @@ def three(dtype):
     return Case(THREE_SIZES, 2, dtype, 960)
 
 
+def widths(dtype):
+    return Case(WIDTH_SIZES, 2, dtype, 980)
+
+
 def all_cases(dtype):
     """(name, case, per-patch family names, per-patch sigma2) of every case of a precision"""
     s2 = SIGMA2[dtype]
@@ -109,7 +124,8 @@ def all_cases(dtype):
            ("addends", with_addends(dtype), ["spline34"] * len(DIAG_SIZES), [s2] * len(DIAG_SIZES)),
            ("split", split(dtype), ["spline34"] * len(SPLIT_SIZES), [s2] * len(SPLIT_SIZES)),
            ("mixed", mixed(dtype), MIXED_NAMES, MIXED_SIGMA2[dtype]),
-           ("three", three(dtype), ["spline34"] * len(THREE_SIZES), [s2] * len(THREE_SIZES))]
+           ("three", three(dtype), ["spline34"] * len(THREE_SIZES), [s2] * len(THREE_SIZES)),
+           ("widths", widths(dtype), ["spline34"] * len(WIDTH_SIZES), [s2] * len(WIDTH_SIZES))]
     return out
 
 

@@ -55,7 +55,7 @@ class Oracle:
     def __init__(self, X, y, eps, hyper, levels=LEVELS):
         self.X, self.y, self.eps, self.levels = X, y, eps, levels
         self.D = X.shape[1]
-        self.bsp = O.BSP(X, levels)
+        self.bsp = self._tree(X, levels)
         self.P = self.bsp.P
         if eps is None:
             off, inds = self.bsp.leaves()
@@ -72,6 +72,11 @@ class Oracle:
         assert all(f["info"] == 0 for f in self.fits)
         self._refits = {}
         self._plans = {}
+
+    def _tree(self, X, levels):
+        """the tree the index lists and the plan are made with: that of X (tests/_append_after_refs.py keeps the tree of
+        the points a model was built on)"""
+        return O.BSP(X, levels)
 
     def cond2(self):
         """cond_2 of U = K + sigma2 I, maximised over the patches"""

@@ -70,7 +70,13 @@ def test_the_cases_cover_the_edges():
     assert (128, 0) in sizes and any(m == 0 and n % 128 for n, m in sizes)
     # every count of 32-row pairs in the last block row, before and after
     assert {((n - 1) % 128) // 32 + 1 for n, _ in sizes} == {1, 2, 3, 4}
-    for n, m in sizes:
+    # every column width of the border kernel, and m on both sides of each switch between two widths
+    every = [nm for _, case, _, _ in AC.all_cases("f64") for nm in case.sizes]
+    assert set(AC.WIDTH_SIZES) <= set(every)
+    assert {AC.column_width(m) for _, m in every if m} == {16, 32, 64, 128}
+    assert {m for _, m in every} >= {16, 17, 32, 33, 64, 65}
+    assert AC.column_width(64) == 64 and sum(1 for _, m in AC.WIDTH_SIZES if AC.column_width(m) == 64) >= 4
+    for n, m in sizes + every:
         assert n + m <= 128 * ((n + 127) // 128)
 
 
