@@ -35,6 +35,7 @@ extern "C" {
 #define PMK_VERSION 103
 #define PMK_MAX_OUTPUTS 16   /* target columns per patch of the multi-output entry points (pmk_model_set_targets_multi) */
 #define PMK_COV_MAX_QUERIES 16384   /* queries of a batch whose joint covariance is asked for (pmk_query_items_cov) */
+#define PMK_REMOVE_MAX_ROWS 32   /* rows one patch can lose in one call (pmk_model_remove) */
 
 /* kernel families = the isbits kernel structs of src/misc/declarations.jl:18-45,65-67,75-111 */
 enum {
@@ -628,7 +629,7 @@ int  pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_
  * one ld_r x 256 strip of the model's type per receiving patch, 8 sum m_r^2 bytes of blocks and the staged items; a failed
  * allocation returns -100 with the bytes asked for in the text.  Stage timers "append_sweep", "append_border" and
  * "append_solve".
- * Out of scope: growing a patch past ld_r (no reallocation), removing points, device-resident x / y arguments, the
+ * Out of scope: growing a patch past ld_r (no reallocation), device-resident x / y arguments, the
  * sharded exchanges, and the leaf lists of the tree itself (pmk_bsp_arrays still describes the points it was built on). */
 /* free_rows[P]: ld_r - n_r, the points patch r can still take */
 int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
@@ -655,6 +656,47 @@ int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
  * n_items = 0 returns 0 and touches nothing. */
 int  pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const double *y, const double *diag,
                       const int32_t *patch, const int64_t *global_index);
+
+/* ---- removing observations from a fitted model in place: row deletion from the Cholesky factor ------------------------
+ * The mirror of the append.  The rows r_1 < ... < r_m of a patch with resident L, z = L^-1 y leave; k0 = r_1, n' = n - m.
+ * L~ = L[keep, :] (n' x n) has L~ L~^T = U[keep, keep] and L~ z = y[keep], and its first k0 rows are lower triangular
+ * already.  New row j of the trailing block B = L[keep >= k0, k0 : n] is the old row k0 + j + s_j (s_j removed rows before
+ * it, 1 <= s_j <= m, non-decreasing) and ends at column j + s_j.  One Householder reflector per new column, of s_j + 1
+ * entries, made from row j without cancellation, the column's sign then flipped so that the diagonal is +|x|, is applied
+ * to the rows below and to z^T[k0:]:  B Q = [L'_22 0],  z' = [ z[:k0] ; (Q^T z[k0:])[:n' - k0] ],  c' = L'^-T z'.
+ * The Cholesky factor is unique, so L' is the factor of the reduced matrix, with the patch's own theta_r and sigma2_r and
+ * its addends; a new diagonal is at least the old one.  One workgroup per patch that loses rows (pmk_remove.hip) moves the
+ * rows of the slab, the coordinates, the targets and the addends up, sweeps the trailing block in blocks of 32 columns
+ * staged in LDS, restores the padding of the rows and columns n' .. n - 1 as a fit leaves it, inverts anew the 32 x 32
+ * -D^-1 blocks from k0 / 32 on and writes n' last; c comes from the back substitution of the fit, run over every patch as
+ * the append runs it.  Rows and columns < k0 of L, z below k0 and the -D^-1 blocks before k0 / 32 keep their bits, and so
+ * do the moved rows left of column k0; removing only the last rows transforms nothing.  Both precisions; works on a model
+ * on the split path.  Memory: the row list of the call, grow only, freed with the model.  Stage timers "remove_rows" and
+ * "remove_solve".
+ * Band rule: nt_r and ld_r are fixed, as for the append, so a patch stays in its last block row:
+ * n'_r >= 128 (nt_r - 1) + 1.  One call removes at most PMK_REMOVE_MAX_ROWS rows from one patch (the reflectors of a
+ * column block are staged in LDS); more rows take more calls.
+ * Out of scope: leaving the last block row in either direction, device-resident arguments, the sharded exchanges, the leaf
+ * lists of the tree itself (pmk_bsp_arrays still describes the points it was built on), renumbering global indices. */
+/* rows[P]: n_r - 128 (nt_r - 1) - 1, the rows patch r can still lose */
+int  pmk_model_removable(pmk_model *m, int64_t *rows);
+/* n_items (patch, row) pairs, host arrays, in any order: row[i] is a row index of patch[i] as it stands BEFORE the call;
+ * the rows that stay keep their order.  On a model of pmk_model_create_from_bsp the entries leave the index list (rebuilt
+ * by one host round trip, prepared before any launch and put in place after); N does not change, the *_global setters
+ * still take N values, and a removed point's value is read by nobody.  The lists stay ascending.  Blocks while the row
+ * list is staged, then enqueues.
+ * A new diagonal that is <= 0 or NaN at new row a sets info[r] = a + 1 if info[r] was 0 (the leading-minor convention of
+ * the fit); the patch is then failed as after a failed fit and no other patch is touched by it.  A patch that had failed
+ * before loses its points, targets and n and stays failed (an info above n'_r becomes n'_r: it names a leading minor).
+ * After the call: leave-one-out values are stale (pmk_model_loo again), the multi-output targets and the trend state are
+ * discarded (pmk_model_set_targets_multi again, with n'_r rows).  The geometry (nt, ld, offsets, schedule, split mode) is
+ * unchanged.  Query objects created earlier keep their plan; their item, gradient and covariance results are stale and
+ * nothing tracks that: run the item stages again.
+ * Refused before any device work, nothing changed: -1 model NULL, not fitted, or built by pmk_model_load; -2 NULL arrays
+ * or n_items < 0; -3 a patch or row out of range, or a (patch, row) given twice (the text names the item); -4 a patch
+ * would fall below 128 (nt - 1) + 1 rows (the text names the patch, its removable rows and the rows asked for); -5 more
+ * than PMK_REMOVE_MAX_ROWS rows of one patch.  n_items = 0 returns 0 and touches nothing. */
+int  pmk_model_remove(pmk_model *m, int64_t n_items, const int32_t *patch, const int64_t *row);
 
 /* query!(Yq, Xq, eta)  src/RKHS/RKHS.jl:220-247 : mean only, Yq = K(Xq, X) c */
 int  pmk_query_mean(pmk_ctx *ctx, const pmk_kernel_desc *th, int D, int64_t n, const double *X,

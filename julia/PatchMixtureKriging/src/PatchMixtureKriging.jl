@@ -22,7 +22,8 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, appendmixtureGP!, capacitymixtureGP
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, appendmixtureGP!, capacitymixtureGP,
+       removemixtureGP!, removablemixtureGP
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -576,6 +577,60 @@ function appendmixtureGP!(η::MixtureGPType{T}, X_new_parts::Vector{Vector{Vecto
         append!(η.X_parts[r], X_new_parts[r])
     end
     η.N_global > 0 && (η.N_global = max(η.N_global, maximum(g) + 1))
+    η.R_multi = 0
+    n = Int[length(X) for X in η.X_parts]
+    empty!(η.U_set.cache); empty!(η.L_set.cache)
+    η.U_set.n = n; η.L_set.n = n
+    info = Vector{Int32}(undef, P)
+    check(ccall((:pmk_model_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}), η.model, info), "pmk_model_info")
+    cs = [Vector{Float64}(undef, n[r]) for r = 1:P]
+    GC.@preserve cs check(ccall((:pmk_model_get_weights, libpmk), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), η.model,
+                                [pointer(c) for c in cs]), "pmk_model_get_weights")
+    for r = 1:P
+        η.c_set[r] = cs[r]
+    end
+    bad = findfirst(!=(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
+    return η
+end
+
+"""removablemixtureGP(η) -> the rows every patch can still lose in place: n_r - 128 (ceil(n_r / 128) - 1) - 1 (a patch stays
+in its last block row of 128)."""
+function removablemixtureGP(η::MixtureGPType)
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before removablemixtureGP"))
+    rows = Vector{Int64}(undef, length(η.X_parts))
+    check(ccall((:pmk_model_removable, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}), η.model, rows), "pmk_model_removable")
+    return rows
+end
+
+"""removemixtureGP!(η, rows_parts) -> η: the rows rows_parts[r] (ONE-based indices into η.X_parts[r] as it stands before
+the call, empty entries allowed, any order) leave patch r of the fitted η, in place: the rows are deleted from the
+resident Cholesky factor, which is not refitted (pmk_model_remove); at most 32 rows of one patch a call.  On an η built
+by MixtureGPType(root, X, ε) a global point of several patches is a row in each, and the library's index list follows;
+N does not change.  c_set, L_set, U_set and X_parts follow; a failed new diagonal throws PosDefException and leaves that
+patch failed until the next fit.  Checked statically only, like the rest of this module."""
+function removemixtureGP!(η::MixtureGPType{T}, rows_parts::Vector{Vector{Int}}) where T
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before removemixtureGP!"))
+    P = length(η.X_parts)
+    length(rows_parts) == P || throw(ArgumentError("one list of rows per patch"))
+    can = removablemixtureGP(η)
+    patch = Int32[]; row = Int64[]
+    for r = 1:P
+        rows = sort(rows_parts[r])
+        allunique(rows) || throw(ArgumentError("patch $r: a row is given twice"))
+        isempty(rows) || (1 <= rows[1] && rows[end] <= length(η.X_parts[r])) ||
+            throw(ArgumentError("patch $r: a row outside 1 .. $(length(η.X_parts[r]))"))
+        length(rows) <= can[r] || throw(ArgumentError("patch $r has $(can[r]) removable rows, $(length(rows)) rows asked for"))
+        for i in rows
+            push!(patch, r - 1); push!(row, i - 1)
+        end
+    end
+    isempty(row) && return η
+    check(ccall((:pmk_model_remove, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int64}),
+        η.model, length(row), patch, row), "pmk_model_remove")
+    for r = 1:P
+        deleteat!(η.X_parts[r], sort(rows_parts[r]))
+    end
     η.R_multi = 0
     n = Int[length(X) for X in η.X_parts]
     empty!(η.U_set.cache); empty!(η.L_set.cache)

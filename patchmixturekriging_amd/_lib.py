@@ -192,6 +192,8 @@ SIGNATURES = {
                                                  C.c_int64]),
     "pmk_model_capacity": (C.c_int, [_vp, _ip]),
     "pmk_model_append": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, _i32p, _ip]),
+    "pmk_model_removable": (C.c_int, [_vp, _ip]),
+    "pmk_model_remove": (C.c_int, [_vp, C.c_int64, _i32p, _ip]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),

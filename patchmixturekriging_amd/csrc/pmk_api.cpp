@@ -152,7 +152,8 @@ int pmk_ctx_create(int device, pmk_ctx **out)
     }
     // kernel attributes are per device: set them for this context's device (current after hipSetDevice above)
     if (pmk::f64::set_device_attributes() || pmk::f32::set_device_attributes() || pmk::set_plan_attributes() ||
-        pmk::f64::set_append_attributes() || pmk::f32::set_append_attributes()) {
+        pmk::f64::set_append_attributes() || pmk::f32::set_append_attributes() || pmk::f64::set_remove_attributes() ||
+        pmk::f32::set_remove_attributes()) {
         pmk_ctx_destroy(c);
         return -100;
     }
@@ -353,6 +354,7 @@ void pmk_model_destroy(pmk_model *m)
 {
     if (!m) return;
     append_release(m);
+    dev_free(m->d_rm_tasks); dev_free(m->d_rm_rows);
     dev_free(m->d_desc); dev_free(m->d_info); dev_free(m->d_hv); dev_free(m->d_hc); dev_free(m->d_pre);
     dev_free(m->d_order); dev_free(m->d_dloo); dev_free(m->d_loo_cnt); dev_free(m->d_ths); dev_free(m->d_sigma2s);
     dev_free(m->d_pidx_off); dev_free(m->d_pidx); dev_free(m->d_gchunk); dev_free(m->d_gstage);

@@ -69,6 +69,13 @@ struct CovTask {
 };
 struct CovPair { int32_t ta, tb; };   // two strips of one region, ta <= tb
 
+// A patch that loses rows (pmk_remove.hip): its rows are rows[first .. first + count), ascending.
+struct RemoveTask {
+    int32_t region;   // local patch
+    int32_t count;    // rows removed (<= PMK_REMOVE_MAX_ROWS)
+    int64_t first;    // first entry of the patch in the row list
+};
+
 // A BSP tree in heap order (root 0, children 2i+1 / 2i+2); leaves numbered left to right.
 struct BspArrays {
     int D = 0, levels = 0;
@@ -198,6 +205,10 @@ struct pmk_model {
     double *d_app_y = nullptr, *d_app_diag = nullptr;      // targets and addends of the staged items
     int32_t *d_app_iota = nullptr;
     int64_t app_x_cap = 0, app_qdiag_cap = 0, app_y_cap = 0, app_diag_cap = 0, app_iota_cap = 0;
+    // pmk_model_remove (pmk_api_remove.cpp, pmk_remove.hip): the tasks and the row list of one call; grow only
+    pmk::RemoveTask *d_rm_tasks = nullptr;
+    int32_t *d_rm_rows = nullptr;
+    int64_t rm_tasks_cap = 0, rm_rows_cap = 0;
 };
 
 struct pmk_query {
@@ -319,6 +330,9 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
     int launch_items_cov(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                    \
     int launch_append_border(pmk_model *m, const pmk_query *q, const double *d_y, const double *d_diag, hipStream_t s); \
     int set_append_attributes();                                                                                     \
+    int launch_remove_rows(pmk_model *m, const RemoveTask *d_tasks, int64_t ntasks, const int32_t *d_rows,           \
+                           hipStream_t s);                                                                           \
+    int set_remove_attributes();                                                                                     \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)

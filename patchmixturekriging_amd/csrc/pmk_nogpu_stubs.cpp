@@ -42,6 +42,8 @@ static int no_gpu(const char *what)
     int launch_items_cov(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_cov"); }  \
     int launch_append_border(pmk_model *, const pmk_query *, const double *, const double *, hipStream_t) { return no_gpu("launch_append_border"); } \
     int set_append_attributes() { return 0; }                                                                       \
+    int launch_remove_rows(pmk_model *, const RemoveTask *, int64_t, const int32_t *, hipStream_t) { return no_gpu("launch_remove_rows"); } \
+    int set_remove_attributes() { return 0; }                                                                       \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)

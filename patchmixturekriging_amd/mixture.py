@@ -540,6 +540,62 @@ class DeviceModel:
             self._X_global = np.ascontiguousarray(np.vstack([self._X_global, Xn]))
         return first, len(point)
 
+    # ---- removing observations from the resident factor in place: row deletion from the Cholesky factor (include/pmk.h)
+    def removable(self):
+        """pmk_model_removable -> int64 [P]: the rows every patch can still lose, n_r - 128 (ceil(n_r / 128) - 1) - 1 (a
+        patch stays in its last block row)"""
+        rows = np.empty(self.P, dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_removable(self.h, _i(rows)), "pmk_model_removable")
+        return rows
+
+    def _remove(self, patch, row):
+        _lib.check(self.ctx.L.pmk_model_remove(self.h, len(row), patch.ctypes.data_as(C.POINTER(C.c_int32)), _i(row)),
+                   "pmk_model_remove")
+        self.n = self.n - np.bincount(patch, minlength=self.P).astype(np.int64)
+        self._loo_done = self._multi_solved = False
+        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+
+    def remove(self, rows_parts):
+        """pmk_model_remove: rows_parts[r] is an integer array (empty allowed) of ZERO-based row indices of patch r as it
+        stands before the call -> info.  L, z and c of the resident factor are reduced in place (no refit), the rows that
+        stay keep their order; loo() and the multi-output targets have to be set again."""
+        self._need_appendable("remove")
+        if getattr(self, "_from_tree", False):
+            raise _lib.PmkError("remove: a model built by from_tree takes remove_global")
+        patch, row, parts = remove_items(rows_parts, self.n)
+        if len(row):
+            self._remove(patch, row)
+            self.X = [np.ascontiguousarray(np.delete(x, p, axis=0)) for x, p in zip(self.X, parts)]
+        return self.info()
+
+    def remove_global(self, indices):
+        """pmk_model_remove on a model built by from_tree: the global points `indices` (zero-based) leave every patch that
+        holds them (patch_index()) -> n_items, the rows removed.  N does not change and the *_global setters still take N
+        values; a point no patch holds is a ValueError.  The tree's own leaf lists are not updated."""
+        self._need_tree_model("remove_global")
+        self._need_appendable("remove_global")
+        g = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(np.unique(g)) != len(g):
+            raise ValueError("remove_global: a global index is given twice")
+        if len(g) and (g.min() < 0 or g.max() >= self.N):
+            raise ValueError("remove_global: a global index outside 0 .. %d" % (self.N - 1))
+        if len(g) == 0:
+            return 0
+        off, inds = self.patch_index()
+        at = np.nonzero(np.isin(inds, g))[0]
+        missing = np.setdiff1d(g, inds[at])
+        if len(missing):
+            raise ValueError("remove_global: no patch holds the global point %d" % int(missing[0]))
+        patch = (np.searchsorted(off, at, side="right") - 1).astype(np.int32)
+        row = np.ascontiguousarray(at - off[patch])
+        check_remove_counts(np.bincount(patch, minlength=self.P), self.n)
+        self._remove(patch, row)
+        keep = np.ones(len(inds), dtype=bool)
+        keep[at] = False
+        self._index = (np.concatenate([[0], np.cumsum(self.n)]).astype(np.int64), inds[keep])
+        self._X = None                      # cut again on first use
+        return len(row)
+
 
 class DeviceQuery:
     """pmk_query: a resident batch of query points and its (query, region) work items"""
@@ -1085,6 +1141,46 @@ def append_items(X_new_parts, y_new_parts, diag_parts, n, D):
     return x, np.ascontiguousarray(np.concatenate(out_y)), diag, patch, out_x
 
 
+MAX_REMOVE_ROWS = 32         # PMK_REMOVE_MAX_ROWS: the rows one patch can lose in one call
+
+
+def check_remove_counts(counts, n):
+    """the rows asked for against the rows every patch can lose, n_r - 128 (ceil(n_r / 128) - 1) - 1, and against
+    MAX_REMOVE_ROWS (ValueError before any device call)"""
+    for r, (m, nr) in enumerate(zip(counts, n)):
+        can = int(nr) - 128 * ((int(nr) + 127) // 128 - 1) - 1
+        if m > can:
+            raise ValueError("patch %d has %d removable rows (n = %d), %d rows asked for" % (r, can, int(nr), int(m)))
+        if m > MAX_REMOVE_ROWS:
+            raise ValueError("%d rows of patch %d in one call, the limit is %d" % (int(m), r, MAX_REMOVE_ROWS))
+
+
+def remove_items(rows_parts, n):
+    """validate the lists of DeviceModel.remove against the patch sizes n -> (patch int32 [T], row int64 [T], parts): the
+    items grouped by patch and every patch's rows, ascending.  ValueError for a wrong length, a non-integer array, a row
+    out of range or given twice, or too many rows, before any device call."""
+    P = len(n)
+    parts = list(rows_parts)
+    if len(parts) != P:
+        raise ValueError("one array of rows per patch: got %d for %d patches" % (len(parts), P))
+    out = []
+    for r in range(P):
+        a = np.asarray(parts[r])
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("patch %d: the rows must be integers, not %s" % (r, a.dtype))
+        a = np.sort(a.astype(np.int64).reshape(-1))
+        if a.size and (a[0] < 0 or a[-1] >= int(n[r])):
+            raise ValueError("patch %d: a row outside 0 .. %d" % (r, int(n[r]) - 1))
+        if a.size > 1 and np.any(np.diff(a) == 0):
+            raise ValueError("patch %d: a row is given twice" % r)
+        out.append(a)
+    counts = np.array([len(a) for a in out], dtype=np.int64)
+    check_remove_counts(counts, n)
+    patch = np.repeat(np.arange(P, dtype=np.int32), counts)
+    row = np.ascontiguousarray(np.concatenate(out)) if P else np.zeros(0, dtype=np.int64)
+    return patch, row, out
+
+
 def fit_patches(X_parts, y_parts, theta, sigma2, ctx=None, dtype="f64"):
     """create + fit + info + weights: the batched path behind fitmixtureGP! and fitRKHS!.  X_parts are POSITIONS: for a
     warp-feature kernel the model is built on the augmented points, and a DPP kernel's point-dependent diagonal term goes
@@ -1211,6 +1307,26 @@ def appendmixtureGP_(eta, X_new_parts, y_new_parts):
         eta.X_parts = model.X
     _store_fit(eta, model, model.weights(), eta.sigma2_set)
     eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the append: fit those again
+    _raise_if_failed(info)
+    return eta
+
+
+def removemixtureGP_(eta, rows_parts):
+    """take observations out of the fitted eta in place -> eta.  rows_parts[r] are the ZERO-based rows of patch r to
+    remove (empty entries allowed; Python indices, as everywhere in this package: the Julia module takes one-based ones);
+    on an eta built by MixtureGPType.from_tree they are ONE array of zero-based GLOBAL point indices, removed from every
+    patch that holds them (DeviceModel.remove_global).  The rows are deleted from the resident factor, which is not
+    refitted; c_set, L_set, U_set and X_parts follow.  Raises PosDefException(patch, k) like fitmixtureGP_ when a new
+    diagonal fails: that patch is then failed as after a failed fit until the next fit."""
+    model = _fitted_model(eta, "removemixtureGP_")
+    if getattr(eta, "_from_tree", False):
+        model.remove_global(rows_parts)
+        info = model.info()
+    else:
+        info = model.remove(rows_parts)
+        eta.X_parts = model.X
+    _store_fit(eta, model, model.weights(), eta.sigma2_set)
+    eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the rows: fit those again
     _raise_if_failed(info)
     return eta
 
