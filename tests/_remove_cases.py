@@ -6,7 +6,8 @@ A case is a list of patches (n points, the rows that leave) of one model.  The s
 deletion can go wrong: the first row (k0 = 0: everything is transformed), the last row (nothing is), rows on both sides of
 a 32-row block and of a 128-row tile, rows spread over three tiles, as many rows as one call takes
 (PMK_REMOVE_MAX_ROWS = 32, more than the 32 reflectors of a column block can be long), the last rows only, a patch of two
-points that keeps one, and a patch that loses nothing.  The geometry (density, families, sigma2) is that of
+points that keeps one, a patch that loses nothing, and the slabs of SLAB_SIZES (full patches, runs of 32 rows, more than
+512 rows below the first removed one).  The geometry (density, families, sigma2) is that of
 tests/_append_cases.py.
 """
 import numpy as np
@@ -31,6 +32,13 @@ MIXED_SIZES = [(33, [0]), (130, [127]), (300, [5, 127, 128, 299]), (40, []), (2,
 # a linear trend has basis functions, and every live 32-row pair is met: rows leave a first, a middle and a last pair
 CONSUMER_SIZES = [(33, [0]), (33, [31]), (130, [0]), (130, [127]), (300, [5, 127, 128, 299]), (300, _CAP_ROWS),
                   (384, [380, 381, 382, 383]), (40, [])]
+# slabs the sweep has to meet as well: a FULL patch (n = ld) that loses its first row, its last row (nothing is transformed)
+# and both; one contiguous run of 32 rows, where s jumps from 0 to 32 at one row and every reflector has 33 entries from
+# the first column on, inside a tile and astride the 128-row tile edge; t = n' - k0 > 512 rows below the first removed one
+# (a third chunk of the row loop), with few rows and with as many as one call takes
+_SPREAD_ROWS = sorted(set([0] + [int(v) for v in np.linspace(19, 599, 31).round()]))
+SLAB_SIZES = [(128, [0]), (128, [127]), (256, [0, 255]), (256, list(range(96, 128))), (300, list(range(100, 132))),
+              (640, [0, 255, 256, 511, 512, 639]), (600, _SPREAD_ROWS)]
 MIXED_NAMES = ["spline34", "gaussian", "rq", "spline12", "rq"]
 MIXED_SIGMA2 = AC.MIXED_SIGMA2
 
@@ -73,4 +81,5 @@ def all_cases(dtype):
             ("addends", Case(DIAG_SIZES, 2, dtype, 1930, addends=True)) + uni(DIAG_SIZES, "spline34"),
             ("split", Case(SPLIT_SIZES, 2, dtype, 1940)) + uni(SPLIT_SIZES, "spline34"),
             ("consumers", Case(CONSUMER_SIZES, 2, dtype, 1960)) + uni(CONSUMER_SIZES, "spline34"),
-            ("mixed", Case(MIXED_SIZES, 2, dtype, 1950), MIXED_NAMES, MIXED_SIGMA2[dtype])]
+            ("mixed", Case(MIXED_SIZES, 2, dtype, 1950), MIXED_NAMES, MIXED_SIGMA2[dtype]),
+            ("slabs", Case(SLAB_SIZES, 2, dtype, 1970)) + uni(SLAB_SIZES, "spline34")]

@@ -15,6 +15,10 @@ One call takes at most PMK_REMOVE_MAX_ROWS = 32 rows of a patch, so 300 -> 257, 
 the cap, the band's edge, and the refusal one row beyond each.
 
 z has no accessor: it is covered by c' (the back substitution of z') and by the bit checks of a later fit.
+
+The `slabs` case of tests/_remove_cases.py goes through the first test like every other: full patches (n = ld) that lose
+their first row, their last row or both, one run of 32 rows inside a tile and astride the tile edge, and more than 512
+rows below the first removed one.  What runs after a removal on a tree-built model is in tests/test_gpu_remove_after.py.
 """
 import ctypes as C
 import json
