@@ -629,10 +629,41 @@ int  pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_
  * one ld_r x 256 strip of the model's type per receiving patch, 8 sum m_r^2 bytes of blocks and the staged items; a failed
  * allocation returns -100 with the bytes asked for in the text.  Stage timers "append_sweep", "append_border" and
  * "append_solve".
- * Out of scope: growing a patch past ld_r (no reallocation), device-resident x / y arguments, the
- * sharded exchanges, and the leaf lists of the tree itself (pmk_bsp_arrays still describes the points it was built on). */
+ * With rows reserved (pmk_model_reserve below) ld_r is larger than 128 ceil(n_r / 128) and the new rows may run on into
+ * the block rows laid out past the patch's last one: everything from 128 nt_r up to ld_r is identity padding, so entering
+ * a block row is the new entries, the -D^-1 blocks of the whole block row entered, and nt_r' = ceil((n_r + m_r) / 128)
+ * written beside n_r + m_r.  The host then follows with what depends on tile counts: max_nt, the factorisation order
+ * (stable, largest first, as at creation), its active prefix, the leave-one-out tasks and the strip workspace.  The split
+ * mode stays as chosen at creation.  The arithmetic on a patch that stays inside its last block row is what it was.
+ * Where the new rows raise max_nt the longer strip workspace is allocated before anything is launched (-100, nothing
+ * changed, if that fails) and put in place together with max_nt; the host flags of "After the call" below are reset
+ * before the tile counts are followed.
+ * Out of scope: device-resident x / y arguments, the sharded exchanges, and the leaf lists of the tree itself
+ * (pmk_bsp_arrays still describes the points it was built on). */
 /* free_rows[P]: ld_r - n_r, the points patch r can still take */
 int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
+/* Room to grow: after the call every patch r has pmk_model_capacity >= rows[r] (host array of P entries).  A patch has
+ * nt_r = ceil(n_r / 128) active block rows and a stride ld_r = 128 nt_cap_r >= 128 nt_r; a model that was never given a
+ * reserve has nt_cap_r = nt_r and behaves as it always did.  Invariant, kept by everything that runs on a model: the rows
+ * and columns of a patch's buffers from 128 nt_r up to ld_r are in the state a fit leaves in padding -- identity in the
+ * slab, 1e300 coordinates, zeros in y, z, c and the addends, -I in the -D^-1 blocks (which are laid out for nt_cap_r block
+ * rows) -- and only this call and pmk_model_append write there.  The fit, the solves and every sweep work on nt_r block
+ * rows whatever the stride.
+ * A patch that has the room keeps its ld_r, none is ever shrunk, and a call that has nothing to grow does nothing.
+ * Otherwise the whole new layout (slabs, coordinates, y, z, c, addends if set, -D^-1 blocks, descriptors) is allocated
+ * beside the old one, written completely by the kernels of pmk_reserve.hip (the active part copied, the rest padding;
+ * 16-byte accesses along the columns), swapped in, and the old one is freed; the offsets and the chunk prefix of the
+ * *_global setters follow.  Blocks.  Works before and after a fit, in both precisions: a fitted model keeps L, z, c, the
+ * -D^-1 blocks, info, the hyperparameters, the tree, the index list and N bit for bit.  As after an append the
+ * leave-one-out values, the multi-output targets and the trend state have to be set again.  Query objects created
+ * earlier keep their plan (every launch reads the model's buffers through the model); their results are stale.
+ * Memory: both layouts exist side by side during the call.  Stage timer "reserve".
+ * -1 NULL argument; -2 a negative entry; -3 the model factors on the split path (its solves read ld_r as the extent;
+ * pmk_test_model_set_split refuses a model that holds reserved rows for the same reason); -4 n_r + rows[r] above 2^24,
+ * the limit at creation; -100 an allocation failed: the model is exactly as it was.
+ * Out of scope: shrinking, the split path, removal out of the last block row (pmk_model_remove keeps its band rule: a
+ * patch that entered a block row with one point cannot lose that point). */
+int  pmk_model_reserve(pmk_model *m, const int64_t *rows);
 /* n_items items (point, target, patch): x host, point-major n_items x D; y host; diag host addends of the kernel's
  * diagonal, or NULL (zeros; -2 if given for a model without pmk_model_set_diag addends); patch[i] the local patch of
  * item i.  The items of one patch become its rows n_r, n_r + 1, ... in the order given; a point of several patches is
@@ -646,13 +677,13 @@ int  pmk_model_capacity(pmk_model *m, int64_t *free_rows);
  * had failed before takes its points, targets and n and stays failed.
  * After the call: leave-one-out values are stale (pmk_model_loo again), the multi-output targets and the trend state are
  * discarded (pmk_model_set_targets_multi again, with n_r + m_r rows, before pmk_model_solve_multi).  The geometry (nt, ld,
- * offsets, schedule, split mode) is unchanged.  Query objects created earlier keep their plan; their item, gradient and
+ * offsets, schedule, split mode) is unchanged unless reserved block rows are entered (above).  Query objects created earlier keep their plan; their item, gradient and
  * covariance results are stale and nothing tracks that: run the item stages again.
  * Refused before any device work, nothing changed: -1 model NULL, not fitted, or built by pmk_model_load (it holds no
  * targets); -2 NULL arrays, global_index given or missing against the model's kind, diag without addends in the model;
  * -3 a patch index out of range, a global index below N or beyond 2^31-3, one given twice for a patch, or the indices of a patch
  * not ascending in the order given (the text names the patch and the index); -4 a patch's
- * capacity exceeded (the text names the patch, its free rows and the rows asked for); -5 more than PMK_COV_MAX_QUERIES items; -6 a non-finite coordinate, target or addend.
+ * capacity exceeded (the text names the patch, its free rows and the rows asked for); -5 more than PMK_COV_MAX_QUERIES items, or more than 128 for one patch (S is factored in an LDS image of 128 x 129; the text names the patch); -6 a non-finite coordinate, target or addend.
  * n_items = 0 returns 0 and touches nothing. */
 int  pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const double *y, const double *diag,
                       const int32_t *patch, const int64_t *global_index);

@@ -42,6 +42,10 @@ int pmk_test_model_set_split(pmk_model *model, int on);
  * receives the padded row count; out == NULL only reports it.  Blocks. */
 int pmk_test_model_packed(pmk_model *model, int64_t patch, int what, int64_t *ld, double *out);
 
+/* the device addresses of the model's slabs, coordinates and weights as integers (tests of pmk_model_reserve: a call
+ * with nothing to grow must not move the model, one that grows a patch moves all of it); never dereferenced */
+int pmk_test_model_buffers(pmk_model *model, int64_t *slabs, int64_t *points, int64_t *weights);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
        querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, appendmixtureGP!, capacitymixtureGP,
-       removemixtureGP!, removablemixtureGP
+       removemixtureGP!, removablemixtureGP, reservemixtureGP!
 
 # ------------------------------------------------------------------------------------------ errors
 struct PMKError <: Exception
@@ -533,12 +533,28 @@ function fitmixtureGP!(Î·::MixtureGPType{T}, y_parts::Vector{Vector{T}}, Î¸, ÏƒÂ
     return Î·
 end
 
-"""capacitymixtureGP(Î·) -> the points every patch can still take in place: ld_r - n_r, ld_r = 128 ceil(n_r / 128)."""
+"""capacitymixtureGP(Î·) -> the points every patch can still take in place: ld_r - n_r, ld_r = 128 ceil(n_r / 128) until
+reservemixtureGP! gives more."""
 function capacitymixtureGP(Î·::MixtureGPType)
     Î·.model == C_NULL && throw(PMKError("fitmixtureGP! must run before capacitymixtureGP"))
     free = Vector{Int64}(undef, length(Î·.X_parts))
     check(ccall((:pmk_model_capacity, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}), Î·.model, free), "pmk_model_capacity")
     return free
+end
+
+"""reservemixtureGP!(Î·, rows) -> Î·: afterwards every patch of the fitted Î· can take rows[r] more points (an Int: the same for
+every patch) through appendmixtureGP!, across 128-row block boundaries, at most 128 per patch and call
+(pmk_model_reserve).  Patches that lack the room get a larger stride: the model moves into a new layout and the old one
+is freed; none is shrunk.  The fit is kept bit for bit.  Checked statically only, like the rest of this module."""
+function reservemixtureGP!(Î·::MixtureGPType, rows::Union{Int,Vector{Int}})
+    Î·.model == C_NULL && throw(PMKError("fitmixtureGP! must run before reservemixtureGP!"))
+    P = length(Î·.X_parts)
+    want = rows isa Int ? fill(Int64(rows), P) : Vector{Int64}(rows)
+    length(want) == P || throw(ArgumentError("one number of rows per patch"))
+    all(>=(0), want) || throw(ArgumentError("a negative number of rows"))
+    check(ccall((:pmk_model_reserve, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}), Î·.model, want), "pmk_model_reserve")
+    Î·.R_multi = 0
+    return Î·
 end
 
 """appendmixtureGP!(Î·, X_new_parts, y_new_parts; global_index_parts) -> Î·: the new points X_new_parts[r] (empty entries

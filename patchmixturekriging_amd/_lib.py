@@ -194,6 +194,7 @@ SIGNATURES = {
     "pmk_model_append": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, _i32p, _ip]),
     "pmk_model_removable": (C.c_int, [_vp, _ip]),
     "pmk_model_remove": (C.c_int, [_vp, C.c_int64, _i32p, _ip]),
+    "pmk_model_reserve": (C.c_int, [_vp, _ip]),
     # include/pmk_test.h
     "pmk_selftest_gemm": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "pmk_selftest_trisolve": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
@@ -201,6 +202,7 @@ SIGNATURES = {
     "pmk_test_comm_force_exchange": (C.c_int, [_vp, C.c_int]),
     "pmk_test_model_set_split": (C.c_int, [_vp, C.c_int]),
     "pmk_test_model_packed": (C.c_int, [_vp, C.c_int64, C.c_int, _ip, _dp]),
+    "pmk_test_model_buffers": (C.c_int, [_vp, _ip, _ip, _ip]),
 }
 
 

@@ -711,8 +711,23 @@ int pmk_model_set_targets(pmk_model *m, const double *const *y)
 int pmk_test_model_set_split(pmk_model *m, int on)
 {
     if (!m) { set_error("pmk_test_model_set_split: model is NULL"); return -1; }
+    for (const PatchDesc &d : m->desc)
+        if (on != 0 && d.ld != d.nt * TILE) {       // the split solves read ld as the patch's extent
+            set_error("pmk_test_model_set_split: the model holds reserved rows (pmk_model_reserve)");
+            return -3;
+        }
     m->split_mode = on != 0 && m->max_nt >= 2;
     m->chain_mode = on == 2 ? 0 : on == 3 ? 1 : -1;
+    return 0;
+}
+
+/* include/pmk_test.h: where the model's buffers are */
+int pmk_test_model_buffers(pmk_model *m, int64_t *slabs, int64_t *points, int64_t *weights)
+{
+    if (!m) { set_error("pmk_test_model_buffers: model is NULL"); return -1; }
+    if (slabs) *slabs = (int64_t)reinterpret_cast<intptr_t>(m->d_a);
+    if (points) *points = (int64_t)reinterpret_cast<intptr_t>(m->d_x);
+    if (weights) *weights = (int64_t)reinterpret_cast<intptr_t>(m->d_c);
     return 0;
 }
 

@@ -79,6 +79,46 @@ static int commit_patch_index(pmk_model *m, NewPatchIndex &idx, int64_t N_new)
     return 0;
 }
 
+// What the host keeps by tile count, after an append has taken patches into block rows that pmk_model_reserve laid out
+// (m->desc[].nt already follows): max_nt, the factorisation order and the active prefix as model_geometry builds them,
+// the leave-one-out tasks (dropped: rebuilt on their next use) and the strip workspace, whose slots are max_nt block rows
+// long and which planned queries use without asking again: `longer` is that workspace for the new max_nt, allocated by
+// the caller before anything was launched (null where max_nt stays or no workspace exists yet), so that nothing in here
+// can leave a planned query with a workspace shorter than its patches.  split_mode stays as chosen at creation.
+static int follow_tile_counts(pmk_model *m, DevTmp<char> &longer)
+{
+    const int64_t P = m->P;
+    hipStream_t s = m->ctx->stream;
+    int max_nt = 0;
+    std::vector<int32_t> order((size_t)P);
+    for (int64_t r = 0; r < P; ++r) {
+        order[(size_t)r] = (int32_t)r;
+        max_nt = std::max(max_nt, (int)m->desc[(size_t)r].nt);
+    }
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t a, int32_t b) { return m->desc[(size_t)a].nt > m->desc[(size_t)b].nt; });
+    m->active_prefix.assign((size_t)max_nt + 2, 0);
+    for (int64_t r = 0; r < P; ++r)
+        for (int t = 0; t <= m->desc[(size_t)r].nt; ++t) ++m->active_prefix[(size_t)t];
+    // first what cannot fail: the workspace and max_nt are a matching pair before anything below returns
+    if (max_nt > m->max_nt) {
+        if (longer.p) {
+            (void)hipFree(m->d_strip);      // waits for the kernels that may still use it
+            m->d_strip = longer.p;
+            longer.p = nullptr;
+        }
+        m->max_nt = max_nt;
+    }
+    m->loo_ntasks = 0;                      // the task list belongs to the old tile counts: built again on its next use
+    if (m->d_loo_tasks) {
+        (void)hipFree(m->d_loo_tasks);
+        m->d_loo_tasks = nullptr;
+    }
+    PMK_HIP(hipMemcpyAsync(m->d_order, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, s));
+    PMK_HIP(hipStreamSynchronize(s));       // `order` is a local
+    return 0;
+}
+
 extern "C" {
 
 int pmk_model_capacity(pmk_model *m, int64_t *free_rows)
@@ -178,6 +218,13 @@ int pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const doubl
             return -4;
         }
     }
+    // the border factors S in an LDS image of TILE x (TILE + 1); only a model with reserved rows can get here
+    for (int64_t r = 0; r < P; ++r)
+        if (count[(size_t)r] > TILE) {
+            set_error("%s: %lld points for patch %lld in one call, the limit is %d per patch", who, (long long)count[(size_t)r],
+                      (long long)r, TILE);
+            return -5;
+        }
 
     // the items grouped by patch, in the order given within a patch; one strip of the sweep per receiving patch
     std::vector<int64_t> first((size_t)P + 1, 0), fill((size_t)P);
@@ -252,6 +299,23 @@ int pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const doubl
     NewPatchIndex new_index;
     if (m->from_bsp)
         if ((rc = prepare_patch_index(m, count, first, hg, new_index))) return rc;
+    // rows that enter new block rows may raise max_nt, and the strip workspace's slots are max_nt block rows long: the
+    // longer one is allocated here, while a failure still leaves the model untouched
+    DevTmp<char> longer_strips;
+    {
+        int64_t new_max_nt = m->max_nt;
+        for (int64_t r = 0; r < P; ++r)
+            new_max_nt = std::max<int64_t>(new_max_nt, (m->desc[(size_t)r].n + count[(size_t)r] + TILE - 1) / TILE);
+        if (new_max_nt > m->max_nt && m->strip_slots > 0) {
+            const int64_t bytes = (int64_t)m->esz * new_max_nt * TILE * TQ * m->strip_slots;
+            if (longer_strips.alloc(bytes)) {
+                (void)hipGetLastError();
+                set_error("%s: hipMalloc of %lld bytes for the strip workspace of %lld block rows failed", who,
+                          (long long)bytes, (long long)new_max_nt);
+                return -100;
+            }
+        }
+    }
 
     c->tic("append_sweep");
     rc = PMK_BY_DTYPE(m, launch_items_cov(q, fitted_theta(m), s));
@@ -264,11 +328,20 @@ int pmk_model_append(pmk_model *m, int64_t n_items, const double *x, const doubl
     // from here on the device holds n + m: the host follows whatever the later calls say
     if (m->from_bsp)
         if ((rc = commit_patch_index(m, new_index, N_new))) return rc;
-    for (int64_t r = 0; r < P; ++r) m->desc[(size_t)r].n += (int32_t)count[(size_t)r];
+    bool crossed = false;
+    for (int64_t r = 0; r < P; ++r) {
+        PatchDesc &d = m->desc[(size_t)r];
+        d.n += (int32_t)count[(size_t)r];
+        const int32_t nt = (d.n + TILE - 1) / TILE;
+        crossed = crossed || nt != d.nt;
+        d.nt = nt;                          // the border has written it into the device descriptor
+    }
     m->loo_valid = false;
     m->R_multi = 0;                         // the target block has n_r rows: pmk_model_set_targets_multi again
     m->multi_solved = false;
     m->trend_q = 0;
+    if (crossed)                            // after the flags: a failure in here must not leave them standing
+        if ((rc = follow_tile_counts(m, longer_strips))) return rc;
     // over every patch: one launch whatever received points, and the split path solves all patches together anyway (it
     // forms z = L^-1 y again from the targets the border has just extended, then c)
     c->tic("append_solve");

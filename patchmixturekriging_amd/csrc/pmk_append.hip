@@ -12,10 +12,14 @@
 //   by 1 and recorded once) with t as one more row, which the elimination turns into the new entries of z,
 //   writes L22 into the diagonal tile (both triangles: zeros above the diagonal), the new coordinates over the 1e300
 //   padding of x, the targets, the addends and z,
-//   inverts anew the 32 x 32 diagonal blocks that meet the rows [n, n + m) (the arithmetic of ninv_from_slab_kernel) and
-//   writes n + m into the device PatchDesc last.
-// Rows and columns < n of the slab, z below n and every other -D^-1 block are not written.  The new rows all lie in the
-// patch's last block row: n > 128 (nt - 1) and n + m <= ld.  c = L'^-T z' is the caller's launch_backsolve.
+//   inverts anew the 32 x 32 diagonal blocks that meet the rows [n, n + m) (the arithmetic of ninv_from_slab_kernel),
+//   and with them the rest of a block row the new rows enter, and
+//   writes nt' = ceil((n + m) / 128) and n + m into the device PatchDesc last.
+// Rows and columns < n of the slab, z below n and every other -D^-1 block are not written.  The new rows start in the
+// patch's last block row, n > 128 (nt - 1), and may run on into the block rows that pmk_model_reserve has laid out past
+// it: m <= 128 and n + m <= ld.  Everything from 128 nt up to ld is identity padding before the call (the invariant of
+// DESIGN.md section 4), so entering a block row is the new entries plus a change of nt.  c = L'^-T z' is the caller's
+// launch_backsolve.
 #include "pmk_real.h"
 
 namespace pmk {
@@ -116,10 +120,15 @@ __global__ __launch_bounds__(AB_THREADS) void append_border_kernel(PatchDesc *de
     if (tid == 0 && sbad != 0 && info[tk.region] == 0) info[tk.region] = n + sbad;
     __threadfence_block();
     __syncthreads();                                    // the new rows of the slab are visible to every wave
-    // -(L[ss])^-1 of the diagonal blocks that meet the new rows: wave w takes block n / 32 + w, one thread per column
-    {
-        const int lane = tid & 63, blk = n / AB_SB + (tid >> 6);
-        if (blk <= (n + m - 1) / AB_SB && lane < AB_SB) {
+    // -(L[ss])^-1 of the diagonal blocks that meet the new rows: wave w takes the blocks n / 32 + w, + 4, ..., one thread
+    // per column.  Rows that enter a new block row (nt2 > nt) take every block up to the end of the last block row
+    // entered: those past the new rows are identity padding and get the blocks a loaded factor has there.  Up to eight
+    // blocks (128 rows meet five, three more in padding).
+    const int nt2 = (n + m + TILE - 1) / TILE;
+    const int last_blk = nt2 > pd.nt ? 4 * nt2 - 1 : (n + m - 1) / AB_SB;
+    for (int blk = n / AB_SB + (tid >> 6); blk <= last_blk; blk += AB_THREADS / 64) {
+        const int lane = tid & 63;
+        if (lane < AB_SB) {
             const int c = lane;
             const real *Dg = Sg + (int64_t)AB_SB * blk + (int64_t)AB_SB * blk * ld;
             real xc[AB_SB];
@@ -135,7 +144,10 @@ __global__ __launch_bounds__(AB_THREADS) void append_border_kernel(PatchDesc *de
             for (int i = 0; i < AB_SB; ++i) out[i + AB_SB * c] = (i >= c) ? -xc[i] : 0.0;
         }
     }
-    if (tid == 0) descs[tk.region].n = n + m;
+    if (tid == 0) {
+        descs[tk.region].nt = nt2;
+        descs[tk.region].n = n + m;
+    }
 }
 
 // per-device kernel attribute (called by pmk_ctx_create beside set_device_attributes): the image of S needs more than

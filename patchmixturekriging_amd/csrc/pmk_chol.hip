@@ -953,7 +953,7 @@ __global__ __launch_bounds__(1024) void chol_backsolve_kernel(const PatchDesc *_
         // and four 128-row chunks of each, 16-byte loads: eight 1 KiB loads in flight per wave (the loop used to keep
         // four 512-byte loads in flight and wait for all of them every pass -- latency bound at 4 TB/s)
         const int64_t i0 = d0 + TILE;
-        const int nrow = (int)(ld - i0);                       // a multiple of TILE
+        const int nrow = (int)((int64_t)pd.nt * TILE - i0);    // a multiple of TILE; the active block rows, not ld
         for (int cc = wave; cc < TILE; cc += 32) {
             const real *colA = S + (d0 + cc) * ld + i0, *colB = colA + 16 * ld;
             const real *cp = cs + i0;
@@ -1022,7 +1022,7 @@ __global__ __launch_bounds__(1024) void chol_backsolve_kernel(const PatchDesc *_
         }
     }
     if (cs_in_lds)
-        for (int i = tid; i < pd.ld; i += 1024) cvec[pd.yoff + i] = cs[i];
+        for (int i = tid; i < pd.nt * TILE; i += 1024) cvec[pd.yoff + i] = cs[i];
 }
 
 // workspace of the split path, grow only

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void cov_gram_kernel(const PatchDesc 
     if (a0 >= ta.count || b0 >= tb.count) return;
     if (pr.ta == pr.tb && b0 + 32 <= a0) return;           // strictly below the diagonal: mirrored from above
     const int li = lane & 15, lg = lane >> 4;
-    const int rows = descs[ta.region].ld;
+    const int rows = descs[ta.region].nt * TILE;           // the rows the strip kernel wrote: the active block rows
     const real *pa = arena + ta.voff + (int64_t)lg * TQ + a0 + li;
     const real *pb = arena + tb.voff + (int64_t)lg * TQ + b0 + li;
     real4_t acc[2][2];

@@ -37,12 +37,13 @@ void set_error(const char *fmt, ...);
 struct PatchDesc {
     int32_t n;        // points in the patch
     int32_t nt;       // ceil(n / TILE)
-    int32_t ld;       // nt * TILE : leading dimension of the slab, padded with identity
+    int32_t ld;       // leading dimension of the slab, a multiple of TILE, >= nt * TILE (more after pmk_model_reserve);
+                      // rows and columns from nt * TILE on are identity and no kernel reads them as part of the patch
     int32_t pad_;
     int64_t aoff;     // element offset of the ld x ld slab (K, then L in place)
     int64_t xoff;     // element offset of the SoA coordinates: x[d][ld]
     int64_t yoff;     // element offset into y / z / c (ld each)
-    int64_t ioff;     // element offset of the negated inverted 32 x 32 diagonal blocks: nt x 4 x (32 x 32)
+    int64_t ioff;     // element offset of the negated inverted 32 x 32 diagonal blocks: (ld / TILE) x 4 x (32 x 32)
 };
 
 // Hyperparameter arguments of the kernels that evaluate theta (K1, the prediction strips, the multi-output means).  The
@@ -333,6 +334,8 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
     int launch_remove_rows(pmk_model *m, const RemoveTask *d_tasks, int64_t ntasks, const int32_t *d_rows,           \
                            hipStream_t s);                                                                           \
     int set_remove_attributes();                                                                                     \
+    int launch_reserve(const pmk_model *m, const PatchDesc *d_new_desc, void *x, void *y, void *z, void *c,          \
+                       void *diag, void *a, void *inv, int64_t max_ld, hipStream_t s);                               \
     }
 PMK_DECLARE_REAL_LAUNCHERS(f64)
 PMK_DECLARE_REAL_LAUNCHERS(f32)

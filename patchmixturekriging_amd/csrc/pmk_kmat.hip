@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void kmat_slab_kernel(const PatchDesc *__restr
         ti = 2 * c + (r > 0);
         tj = 2 * c + (r > 1);
     } else {
-        const int nt64 = pd.ld / 64;
+        const int nt64 = pd.nt * (TILE / 64);     // the active block rows: what lies past them up to ld stays identity
         const int ntiles = nt64 * (nt64 + 1) / 2;
         const int t = blockIdx.x;
         if (t >= ntiles) return;

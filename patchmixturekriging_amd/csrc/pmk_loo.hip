@@ -79,7 +79,7 @@ __global__ __launch_bounds__(STRIP_THREADS, 2) void loo_strip_kernel(const Patch
         const LooTask tk = tasks[task];
         const PatchDesc pd = descs[tk.patch];
         const int i0 = 2 * tk.strip;
-        const int count = min(TQ, pd.ld - TQ * tk.strip);   // 128 in the last strip of a patch with an odd tile count
+        const int count = min(TQ, pd.nt * TILE - TQ * tk.strip);   // 128 in the last strip of a patch with an odd tile count
         const bool active = STRIP_WCOLS * wave < count;            // wave-uniform
         const int w0 = i0 + half;                            // first block row in which this wave's columns are not zero
         const real *S = A + pd.aoff;

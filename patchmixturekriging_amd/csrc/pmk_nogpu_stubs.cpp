@@ -44,6 +44,7 @@ static int no_gpu(const char *what)
     int set_append_attributes() { return 0; }                                                                       \
     int launch_remove_rows(pmk_model *, const RemoveTask *, int64_t, const int32_t *, hipStream_t) { return no_gpu("launch_remove_rows"); } \
     int set_remove_attributes() { return 0; }                                                                       \
+    int launch_reserve(const pmk_model *, const PatchDesc *, void *, void *, void *, void *, void *, void *, void *, int64_t, hipStream_t) { return no_gpu("launch_reserve"); } \
     }
 PMK_STUB_REAL(f64)
 PMK_STUB_REAL(f32)

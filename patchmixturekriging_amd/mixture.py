@@ -154,12 +154,13 @@ class DeviceModel:
         self._has_kernels = False       # a fit records its kernels; a model built from factors needs set_kernels
 
     @classmethod
-    def from_tree(cls, root, X, y=None, eps=None, ctx=None, dtype="f64", leaf_base=0, P=None):
+    def from_tree(cls, root, X, y=None, eps=None, ctx=None, dtype="f64", leaf_base=0, P=None, reserve=None):
         """pmk_model_create_from_bsp: the model of the tree `root` and ONE global point array X (N, D), numpy or a device
         array (a torch tensor), float64 and contiguous; y likewise, N targets, or None (zero until set_targets_global).
         eps=None: patch r is the tree's own leaf leaf_base + r; eps >= 0: its eps-set (organizetrainingsets).  The
         library assigns, gathers and packs on the GPU; the tree is attached.  The result equals
-        DeviceModel(X_set, y_set) on the host-cut lists bit for bit."""
+        DeviceModel(X_set, y_set) on the host-cut lists bit for bit.  reserve: rows for reserve(), straight after
+        creation."""
         xa = GlobalArray(X, "X").points(getattr(root, "_D", None))
         N = xa.shape[0]
         ya = None if y is None else GlobalArray(y, "y").vector(N)
@@ -190,6 +191,8 @@ class DeviceModel:
         self.theta = self.sigma2 = None
         self._has_factor, self._has_targets = False, True
         self._loo_done = self._multi_solved = self._has_kernels = False
+        if reserve is not None:
+            self.reserve(reserve)
         return self
 
     @property
@@ -468,10 +471,25 @@ class DeviceModel:
 
     # ---- appending observations to the resident factor in place: the border of the Cholesky factor (include/pmk.h)
     def capacity(self):
-        """pmk_model_capacity -> int64 [P]: the points every patch can still take, ld_r - n_r with ld_r = 128 ceil(n_r / 128)"""
+        """pmk_model_capacity -> int64 [P]: the points every patch can still take, ld_r - n_r; ld_r = 128 ceil(n_r / 128)
+        until reserve() gives more"""
         free = np.empty(self.P, dtype=np.int64)
         _lib.check(self.ctx.L.pmk_model_capacity(self.h, _i(free)), "pmk_model_capacity")
         return free
+
+    def reserve(self, rows):
+        """pmk_model_reserve: afterwards capacity() >= rows, an int for every patch or one value per patch -> capacity().
+        Patches that lack the room get a larger stride ld_r (the model moves into a new layout, the old one is freed); none
+        is shrunk.  Works before and after a fit; a fitted model keeps its factor, weights and info bit for bit.  loo(), the
+        multi-output targets and the trend state have to be set again; queries created earlier keep their plan."""
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(rows), (self.P,)) if np.ndim(rows) == 0 else rows)
+        if rows.shape != (self.P,) or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be an int or %d ints, one per patch" % self.P)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        _lib.check(self.ctx.L.pmk_model_reserve(self.h, _i(rows)), "pmk_model_reserve")
+        self._loo_done = self._multi_solved = False
+        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+        return self.capacity()
 
     def _need_appendable(self, who):
         self._need()
@@ -493,7 +511,7 @@ class DeviceModel:
         self._need_appendable("append")
         if getattr(self, "_from_tree", False):
             raise _lib.PmkError("append: a model built by from_tree takes append_global")
-        x, y, diag, patch, parts = append_items(X_new_parts, y_new_parts, diag_parts, self.n, self.D)
+        x, y, diag, patch, parts = append_items(X_new_parts, y_new_parts, diag_parts, self.n, self.D, self.capacity())
         if len(y):
             self._append(x, y, diag, patch, None)
             self.X = [np.ascontiguousarray(np.vstack([a, b])) for a, b in zip(self.X, parts)]
@@ -531,7 +549,7 @@ class DeviceModel:
             _lib.check(L.pmk_bsp_assign(h, m, _d(Xn), self._eps, _i(off), _i(inds), _i(loff), _i(lists)), "pmk_bsp_assign")
             point = np.repeat(np.arange(m, dtype=np.int64), np.diff(loff))     # point-major: ascending within a patch
             patch = lists[:int(loff[-1])].copy()
-        check_append_counts(np.bincount(patch, minlength=self.P), self.n)
+        check_append_counts(np.bincount(patch, minlength=self.P), self.n, self.capacity())
         self._append(np.ascontiguousarray(Xn[point]), np.ascontiguousarray(yn[point]), None, patch.astype(np.int32),
                      np.ascontiguousarray(first + point))
         self.N = first + m
@@ -1090,20 +1108,24 @@ def patch_hyper(thetas, sigma2s, P):
 
 
 MAX_APPEND_ITEMS = 16384     # PMK_COV_MAX_QUERIES: the appended items run through the covariance sweep
+MAX_APPEND_PATCH_ROWS = 128  # the points one patch can take in one call (the border factors S in one LDS tile)
 
 
-def check_append_counts(counts, n):
-    """the rows asked for against the free rows ld_r - n_r of every patch, ld_r = 128 ceil(n_r / 128), and the items of
-    one call against MAX_APPEND_ITEMS (ValueError before any device call)"""
+def check_append_counts(counts, n, free_rows=None):
+    """the rows asked for against the free rows ld_r - n_r of every patch (free_rows: DeviceModel.capacity(); None: a model
+    without reserved rows, ld_r = 128 ceil(n_r / 128)), against MAX_APPEND_PATCH_ROWS, and the items of one call against
+    MAX_APPEND_ITEMS (ValueError before any device call)"""
     for r, (m, nr) in enumerate(zip(counts, n)):
-        free = 128 * ((int(nr) + 127) // 128) - int(nr)
+        free = 128 * ((int(nr) + 127) // 128) - int(nr) if free_rows is None else int(free_rows[r])
         if m > free:
             raise ValueError("patch %d has %d free rows (n = %d), %d rows asked for" % (r, free, int(nr), int(m)))
+        if m > MAX_APPEND_PATCH_ROWS:
+            raise ValueError("%d points for patch %d in one call, the limit is %d per patch" % (int(m), r, MAX_APPEND_PATCH_ROWS))
     if int(np.sum(counts)) > MAX_APPEND_ITEMS:
         raise ValueError("%d items in one call, the limit is %d" % (int(np.sum(counts)), MAX_APPEND_ITEMS))
 
 
-def append_items(X_new_parts, y_new_parts, diag_parts, n, D):
+def append_items(X_new_parts, y_new_parts, diag_parts, n, D, free_rows=None):
     """validate the lists of DeviceModel.append against the patch sizes n and the dimension D -> (x [T, D], y [T],
     diag [T] or None, patch int32 [T], parts): the items grouped by patch, and the new points of every patch as (m_r, D)
     arrays.  ValueError for a wrong length, shape, a non-finite value or a full patch, before any device call."""
@@ -1134,7 +1156,7 @@ def append_items(X_new_parts, y_new_parts, diag_parts, n, D):
         out_y.append(y)
         out_d.append(d)
     counts = np.array([len(y) for y in out_y], dtype=np.int64)
-    check_append_counts(counts, n)
+    check_append_counts(counts, n, free_rows)
     patch = np.repeat(np.arange(P, dtype=np.int32), counts)
     x = np.ascontiguousarray(np.vstack(out_x)) if P else np.zeros((0, D))
     diag = None if ds is None else np.ascontiguousarray(np.concatenate(out_d))
@@ -1228,12 +1250,13 @@ class MixtureGPType:
         self.L_set = _LazyFactors(self, GET_L)      # cholesky(U).L    (mixtureGP.jl:112)
 
     @classmethod
-    def from_tree(cls, root, X, eps=None, hps=None, ctx=None, dtype="f64"):
+    def from_tree(cls, root, X, eps=None, hps=None, ctx=None, dtype="f64", reserve=None):
         """MixtureGPType on the patches of a tree, built on the device from ONE global point array (numpy or a device
         array): DeviceModel.from_tree.  eps=None: the tree's leaves (setuppartition); eps >= 0: the eps-sets
         (organizetrainingsets).  On such an eta fitmixtureGP_ / _multi_ / _patches_ take the GLOBAL targets (N values, or
-        N x R) and refit this resident model: no model is created per call."""
-        model = DeviceModel.from_tree(root, X, None, eps, ctx, dtype)
+        N x R) and refit this resident model: no model is created per call.  reserve: rows every patch (an int) or each
+        patch can still take through appendmixtureGP_ (DeviceModel.reserve)."""
+        model = DeviceModel.from_tree(root, X, None, eps, ctx, dtype, reserve=reserve)
         self = cls.__new__(cls)
         self._from_tree = True
         self._X_parts = None
@@ -1308,6 +1331,16 @@ def appendmixtureGP_(eta, X_new_parts, y_new_parts):
     _store_fit(eta, model, model.weights(), eta.sigma2_set)
     eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the append: fit those again
     _raise_if_failed(info)
+    return eta
+
+
+def reservemixtureGP_(eta, rows):
+    """room for appendmixtureGP_ in the resident model of eta -> eta: afterwards every patch can take `rows` more points
+    (an int, or one value per patch), across 128-row block boundaries, at most 128 per patch and call
+    (DeviceModel.reserve).  The fit is kept bit for bit; on an eta built by MixtureGPType.from_tree the call also works
+    before the first fit."""
+    model = eta._tree_model if getattr(eta, "_from_tree", False) else _fitted_model(eta, "reservemixtureGP_")
+    model.reserve(rows)
     return eta
 
 
