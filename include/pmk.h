@@ -83,7 +83,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad", "items_cov", "mix_cov"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad", "items_cov", "mix_cov", "cov_trend"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -589,8 +589,8 @@ int  pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weigh
  * give exact zeros.  A patch with info != 0 gives NaN in its whole block and in the whole row and column of every query
  * that blends one of its items.  This is the single-output path: it ignores the trend, as pmk_query_items does, and does
  * not depend on targets; it needs a resident factor only, so models of pmk_model_load + pmk_model_set_kernels serve too.
- * Out of scope: a trend's term z . z', the sharded and all-gather exchanges (the model must hold every leaf), and fusing
- * the means into the covariance sweep.  Every family is admitted (nothing here differentiates), PMK_MODSQEXP at D = 1 only.
+ * Out of scope: a trend's term z . z' (here: pmk_query_items_cov_multi below adds it), the sharded and all-gather exchanges
+ * (the model must hold every leaf), and fusing the means into the covariance sweep.  Every family is admitted (nothing here differentiates), PMK_MODSQEXP at D = 1 only.
  * Memory, owned by the query, grow only: sum over strips of ld x 256 elements of the model's type (a region's items are
  * dealt over ceil(m_r / 256) strips, ld the padded size of its patch), 8 sum m_r^2 bytes of blocks and 8 Nq^2 bytes of
  * result; a failed allocation returns -100 with the bytes asked for in the text.  Stage timers "items_cov" (sweep, Gram and
@@ -615,6 +615,39 @@ int  pmk_query_get_items_cov(pmk_query *q, int64_t region, int64_t *m, int32_t *
  * fetches.  Any output pointer may be NULL; with Cov NULL no covariance stage runs. */
 int  pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                     double radius, double delta, double *Yq, double *Vq, double *Cov, int64_t ldc);
+
+/* ---- the joint covariance on the multi-output path: under a trend, and for R target columns -------------------------------
+ * A model solved with a trend (pmk_model_set_trend + pmk_model_solve_multi) predicts as a universal-kriging predictor, and
+ * its joint covariance carries the drift's uncertainty: with H the basis of a patch, C_H = U^-1 H, G = H^T C_H = L_G L_G^T,
+ *   S_r[a, b] = k_r(x_a, x_b) - V_a . V_b + z_a . z_b,   z = L_G^-1 rho,   rho = h(x) - C_H^T k_r(X_r, x),
+ *   S_r[a, a] = max( k_r(x_a, x_a) + the addend of pmk_query_set_diag - |V_a|^2, min_v ) + |z_a|^2,
+ * the trend's term after the clamp, as the item variance of pmk_query_items_multi has it: the diagonal of the blend is the
+ * Vq of pmk_query_fetch_multi up to rounding (and the cross term of a query with two items of one region).  The blend is
+ * that of pmk_query_mix_cov.  The covariance does not depend on the targets: the R columns are independent fields with a
+ * common kernel and share it.  z comes from a = kq^T C_H, which pmk_query_items_multi leaves in the item rows, through the
+ * operations of the item variance; z_a . z_b is one chain of fused multiply-adds in ascending basis index, added to the
+ * entry with one addition, so the bit promises of pmk_query_items_cov hold here too.  A patch whose trend is flagged
+ * (pmk_model_trend_info != 0) answers as one whose factorisation failed: NaN in its block and in the row and column of
+ * every query that blends it.  Memory: 40 bytes per item and 4 bytes per patch on top of pmk_query_items_cov's, owned by
+ * the query, grow only.  Out of scope: the sharded and all-gather exchanges, fusing the means into the sweep, and batches
+ * above PMK_COV_MAX_QUERIES. */
+/* the region blocks of the current plan on the multi-output path.  th: the kernel that was given to the items call, or NULL
+ * for the model's own (the library does not compare the two).  Runs what pmk_query_items_cov runs and then, if the model's
+ * trend has q > 0, the trend's term; with no trend in force the blocks are those of pmk_query_items_cov bit for bit.
+ * Enqueues.  pmk_query_mix_cov, pmk_query_fetch_cov(_dev) and pmk_query_get_items_cov serve its results unchanged; new
+ * items discard them.  Serves a query made by pmk_query_create_items too (the joint universal-kriging covariance of
+ * explicit points against one patch).  Stage timer "cov_trend", inside "items_cov".  Before any launch: -1: no plan or no
+ * resident factor; -2: the last items on this plan are not those of pmk_query_items_multi / _multi_fitted, or they were
+ * computed under another trend (run the items again), or unknown family, PMK_MODSQEXP with D > 1; -3: the multi-output
+ * weights are stale (pmk_model_solve_multi), th NULL on a model that holds no kernels, or the model does not hold every
+ * leaf; -5: Nq > PMK_COV_MAX_QUERIES; -100: an allocation failed (the text gives the bytes asked for). */
+int  pmk_query_items_cov_multi(pmk_query *q, const pmk_kernel_desc *th);
+/* one-shot: create + plan + pmk_query_items_multi_fitted (variance iff Vq) + pmk_query_mix_multi +
+ * pmk_query_items_cov_multi(NULL) + pmk_query_mix_cov + the fetches.  Yq is Nq x R column-major with ldyq >= Nq.  Any output
+ * pointer may be NULL; with Cov NULL no covariance stage runs. */
+int  pmk_predict_mixture_cov_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                          double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *Cov,
+                                          int64_t ldc);
 
 /* ---- appending observations to a fitted model in place: the border of the Cholesky factor ---------------------------
  * A patch's buffers are laid out for ld_r = 128 ceil(n_r / 128) rows, so up to ld_r - n_r new points fit without moving

@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, appendmixtureGP!, capacitymixtureGP,
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, querymixtureGP_cov_multi, appendmixtureGP!, capacitymixtureGP,
        removemixtureGP!, removablemixtureGP, reservemixtureGP!
 
 # ------------------------------------------------------------------------------------------ errors
@@ -1203,6 +1203,47 @@ function querymixtureGP_cov(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float
         check(ccall((:pmk_query_get_items_cov, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64),
                     q[], region - 1, Ptr{Int64}(C_NULL), query, S, max(m[], 1)), "pmk_query_get_items_cov")
         return Yq, Vq, Cov, query .+ Int32(1), S
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""querymixtureGP_cov_multi(Xq, η, root, levels, radius, δ, weight_θ; staged = false) -> (Yq, Vq, Cov): the R blended means
+(Nq x R) and the variance of querymixtureGPmulti! with the model's own kernels, and the joint posterior covariance Cov
+(Nq x Nq, symmetric) of the batch, for the columns of fitmixtureGPmulti! with the trend of settrendmixtureGP! if one is set
+(pmk_predict_mixture_cov_multi_fitted).  Under a trend Cov is the universal-kriging covariance and its diagonal is Vq up to
+rounding; the R columns are independent fields and share it.  staged = true runs the staged calls instead
+(pmk_query_items_cov_multi); the results are the same.  At most 16384 queries."""
+function querymixtureGP_cov_multi(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float64}, root, levels, radius::Float64,
+                                  δ::Float64, weight_θ; staged::Bool = false)
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_cov_multi"))
+    R = η.R_multi
+    R >= 1 || throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_cov_multi"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    Yq = Matrix{Float64}(undef, Nq, R); Vq = Vector{Float64}(undef, Nq); Cov = Matrix{Float64}(undef, Nq, Nq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    if !staged
+        check(ccall((:pmk_predict_mixture_cov_multi_fitted, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64},
+                     Ptr{Float64}, Int64),
+                    η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, Yq, max(Nq, 1), Vq, Cov, max(Nq, 1)),
+              "pmk_predict_mixture_cov_multi_fitted")
+        return Yq, Vq, Cov
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_items_multi_fitted, libpmk), Cint, (Ptr{Cvoid}, Cint), q[], 1), "pmk_query_items_multi_fitted")
+        check(ccall((:pmk_query_mix_multi, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int64), q[], Ref(desc(weight_θ)), 0, Nq),
+              "pmk_query_mix_multi")
+        check(ccall((:pmk_query_items_cov_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}), q[], Ptr{KernelDesc}(C_NULL)),
+              "pmk_query_items_cov_multi")
+        check(ccall((:pmk_query_mix_cov, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}), q[], Ref(desc(weight_θ))), "pmk_query_mix_cov")
+        check(ccall((:pmk_query_fetch_multi, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), q[], Yq, max(Nq, 1), Vq),
+              "pmk_query_fetch_multi")
+        check(ccall((:pmk_query_fetch_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], Cov, max(Nq, 1)), "pmk_query_fetch_cov")
+        return Yq, Vq, Cov
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end

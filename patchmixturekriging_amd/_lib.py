@@ -190,6 +190,9 @@ SIGNATURES = {
     "pmk_query_get_items_cov": (C.c_int, [_vp, C.c_int64, _ip, _i32p, _dp, C.c_int64]),
     "pmk_predict_mixture_cov_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp, _dp,
                                                  C.c_int64]),
+    "pmk_query_items_cov_multi": (C.c_int, [_vp, _kp]),
+    "pmk_predict_mixture_cov_multi_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64,
+                                                       _dp, _dp, C.c_int64]),
     "pmk_model_capacity": (C.c_int, [_vp, _ip]),
     "pmk_model_append": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, _i32p, _ip]),
     "pmk_model_removable": (C.c_int, [_vp, _ip]),

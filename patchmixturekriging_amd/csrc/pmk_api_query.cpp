@@ -282,8 +282,8 @@ void pmk_query_destroy(pmk_query *q)
     dev_free(q->d_um); dev_free(q->d_yqm); dev_free(q->d_mcpre); dev_free(q->d_gm); dev_free(q->d_dyq);
     dev_free(q->d_gv); dev_free(q->d_gh); dev_free(q->d_dvq); dev_free(q->d_vgpre);
     dev_free(q->d_cov_v); dev_free(q->d_cov_s); dev_free(q->d_cov); dev_free(q->d_cov_tasks); dev_free(q->d_cov_pairs);
-    dev_free(q->d_cov_goff);
-    dev_free(q->d_loo_x);               // base of the leave-one-out arena (loo_reserve)
+    dev_free(q->d_cov_goff); dev_free(q->d_cov_z); dev_free(q->d_cov_flags);
+    dev_free(q->d_loo_x);              // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
 }
@@ -1063,15 +1063,32 @@ static int fetch_cov_common(pmk_query *q, double *Cov, int64_t ldc, hipMemcpyKin
     return 0;
 }
 
-extern "C" {
-
-int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
+// The region blocks of the current plan.  multi: the multi-output path (pmk_query_items_cov_multi), whose blocks carry the
+// term z_a . z_b of the model's trend; its checks come before any launch, and with no trend in force it runs what the
+// single-output call runs.
+static int items_cov_common(pmk_query *q, const pmk_kernel_desc *th, bool multi, const char *who)
 {
-    static const char who[] = "pmk_query_items_cov";
     if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
     pmk_model *m = q->m;
     if (!m->fitted) { set_error("%s: the model holds no resident factor", who); return -1; }
     if (int rc = whole_tree_ok(m, who, COV_NEEDS_ALL, -3)) return rc;
+    if (multi) {
+        if (!m->multi_solved) {
+            set_error("%s: pmk_model_solve_multi has not run on the resident factor (the multi-output weights are stale)", who);
+            return -3;
+        }
+        if (q->R_items < 1 || !q->items_fn) {
+            set_error("%s: the last items on this plan must be those of pmk_query_items_multi or _multi_fitted (a member "
+                      "item of pmk_query_items_loo_multi is a lookup, not a function of x)", who);
+            return -2;
+        }
+        if (q->um_ld - q->R_items != m->trend_q) {
+            set_error("%s: the items were computed under a trend with q = %d, the model's has q = %d: run the items again",
+                      who, q->um_ld - q->R_items, m->trend_q);
+            return -2;
+        }
+    }
+    const int qt = multi ? m->trend_q : 0;
     if (th) {
         if (int rc = cov_kernel_ok(th, m->D, who, "theta")) return rc;
     } else {
@@ -1085,6 +1102,7 @@ int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
     PMK_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     q->cov_items = q->mixed_cov = false;
+    q->cov_trend_q = 0;
     std::vector<CovTask> tasks;
     std::vector<CovPair> pairs;
     const int64_t velems = cov_tasks_from_plan(q, tasks, pairs);
@@ -1095,6 +1113,10 @@ int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
     if (int rc = grow_sized(q->d_cov_tasks, q->cov_tasks_cap, q->cov_ntasks, s, who, "the strip tasks")) return rc;
     if (int rc = grow_sized(q->d_cov_pairs, q->cov_pairs_cap, q->cov_npairs, s, who, "the strip pairs")) return rc;
     if (int rc = grow_sized(q->d_cov_goff, q->cov_goff_cap, m->P + 1, s, who, "the block offsets")) return rc;
+    if (qt > 0) {
+        if (int rc = grow_sized(q->d_cov_z, q->cov_z_cap, q->total * TQ_MAX, s, who, "the items' trend vectors")) return rc;
+        if (int rc = grow_sized(q->d_cov_flags, q->cov_flags_cap, m->P, s, who, "the patch marks")) return rc;
+    }
     PMK_HIP(hipMemcpyAsync(q->d_cov_goff, q->cov_goff.data(), sizeof(int64_t) * q->cov_goff.size(), hipMemcpyHostToDevice, s));
     if (!tasks.empty()) {
         PMK_HIP(hipMemcpyAsync(q->d_cov_tasks, tasks.data(), sizeof(CovTask) * tasks.size(), hipMemcpyHostToDevice, s));
@@ -1102,11 +1124,30 @@ int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
     }
     PMK_HIP(hipStreamSynchronize(s));       // `tasks` and `pairs` are locals
     c->tic("items_cov");
-    const int rc = PMK_BY_DTYPE(m, launch_items_cov(q, th, s));
+    int rc = PMK_BY_DTYPE(m, launch_items_cov(q, th, s));
+    // S[a, b] += z_a . z_b, on the diagonal after the clamp at min_v
+    if (!rc && qt > 0) {
+        c->tic("cov_trend");
+        rc = launch_cov_trend(q, s);
+        c->toc("cov_trend");
+    }
     c->toc("items_cov");
     if (rc) return rc;
     q->cov_items = true;
+    q->cov_trend_q = qt;
     return 0;
+}
+
+extern "C" {
+
+int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
+{
+    return items_cov_common(q, th, false, "pmk_query_items_cov");
+}
+
+int pmk_query_items_cov_multi(pmk_query *q, const pmk_kernel_desc *th)
+{
+    return items_cov_common(q, th, true, "pmk_query_items_cov_multi");
 }
 
 int pmk_query_mix_cov(pmk_query *q, const pmk_kernel_desc *weight_th)
@@ -1189,6 +1230,36 @@ int pmk_predict_mixture_cov_fitted(pmk_model *m, const pmk_kernel_desc *weight_t
         [&](pmk_query *q) { int rc = pmk_query_items_fitted(q); return !rc && Cov ? pmk_query_items_cov(q, nullptr) : rc; },
         [&](pmk_query *q) { int rc = pmk_query_mix(q, weight_th, 0, Nq); return !rc && Cov ? pmk_query_mix_cov(q, weight_th) : rc; },
         [&](pmk_query *q) { int rc = pmk_query_fetch(q, Yq, Vq); return !rc && Cov ? pmk_query_fetch_cov(q, Cov, ldc) : rc; });
+}
+
+int pmk_predict_mixture_cov_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                         double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *Cov,
+                                         int64_t ldc)
+{
+    static const char who[] = "pmk_predict_mixture_cov_multi_fitted";
+    if (!m) { set_error("%s: model is NULL", who); return -1; }
+    if (int rc = whole_tree_ok(m, who, COV_NEEDS_ALL, -3)) return rc;
+    if ((Yq && ldyq < Nq) || (Cov && ldc < Nq)) {
+        set_error("%s: ldyq = %lld or ldc = %lld < Nq = %lld", who, (long long)ldyq, (long long)ldc, (long long)Nq);
+        return -4;
+    }
+    if (Cov)
+        if (int rc = cov_batch_ok(Nq, who)) return rc;
+    // with Cov NULL no covariance stage runs
+    return one_shot(
+        m, Nq, Xq, radius, delta,
+        [&](pmk_query *q) {
+            int rc = pmk_query_items_multi_fitted(q, Vq != nullptr);
+            return !rc && Cov ? pmk_query_items_cov_multi(q, nullptr) : rc;
+        },
+        [&](pmk_query *q) {
+            int rc = pmk_query_mix_multi(q, weight_th, 0, Nq);
+            return !rc && Cov ? pmk_query_mix_cov(q, weight_th) : rc;
+        },
+        [&](pmk_query *q) {
+            int rc = (Yq || Vq) ? pmk_query_fetch_multi(q, Yq, ldyq, Vq) : 0;
+            return !rc && Cov ? pmk_query_fetch_cov(q, Cov, ldc) : rc;
+        });
 }
 
 }  // extern "C"

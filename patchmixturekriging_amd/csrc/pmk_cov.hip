@@ -379,8 +379,10 @@ int launch_mix_cov(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s)
     if (q->Nq == 0) return 0;
     const pmk_model *m = q->m;
     const unsigned nt = (unsigned)((q->Nq + MIXC - 1) / MIXC);
+    // blocks with a trend's term: a patch whose trend is flagged marks its queries as one whose factorisation failed does
+    const int32_t *info = q->cov_trend_q > 0 ? q->d_cov_flags : (const int32_t *)m->d_info;
     hipLaunchKernelGGL(mix_cov_kernel, dim3(nt, nt), dim3(MIXC * MIXC), 0, s, q->Nq, q->d_qoff, q->d_item_t, q->d_item_region,
-                       q->d_item_pos, q->d_roff, q->d_cov_goff, q->d_cov_s, (const int32_t *)m->d_info, wth, q->d_cov);
+                       q->d_item_pos, q->d_roff, q->d_cov_goff, q->d_cov_s, info, wth, q->d_cov);
     PMK_HIP(hipGetLastError());
     return 0;
 }

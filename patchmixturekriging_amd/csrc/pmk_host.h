@@ -137,12 +137,18 @@ inline void reset_item_state(pmk_query *q)
     q->mixed_multi = false;
     q->items_fn = q->grad_items = q->mixed_grad = false;
     q->vgrad_items = q->mixed_vgrad = false;
+    // blocks with a trend's term (pmk_query_items_cov_multi) were computed from the item rows that now go
+    if (q->cov_trend_q > 0) {
+        q->cov_items = q->mixed_cov = false;
+        q->cov_trend_q = 0;
+    }
 }
 // a new plan or new explicit items (not new item values: the covariance does not depend on them) discard the covariance
 inline void reset_plan_state(pmk_query *q)
 {
     reset_item_state(q);
     q->cov_items = q->mixed_cov = false;
+    q->cov_trend_q = 0;
 }
 
 // The one-shot calls: a query object for Xq, its plan, the three stages as the caller gives them, and the object goes

@@ -276,6 +276,12 @@ struct pmk_query {
     pmk::CovPair *d_cov_pairs = nullptr; int64_t cov_pairs_cap = 0, cov_npairs = 0;
     int64_t *d_cov_goff = nullptr; int64_t cov_goff_cap = 0;      // P + 1
     std::vector<int64_t> cov_goff;      // host copy: prefix of m_r^2
+    // the trend's term of the blocks (pmk_query_items_cov_multi, pmk_cov_trend.hip).  cov_trend_q > 0: the blocks carry
+    // z_a . z_b of a trend with that many basis functions, computed from the item rows of pmk_query_items_multi, and the
+    // blend reads d_cov_flags in place of the model's info; new items discard such blocks, pmk_query_items_cov replaces them
+    int cov_trend_q = 0;
+    double *d_cov_z = nullptr; int64_t cov_z_cap = 0;             // sorted items x TQ_MAX: z = L_G^-1 rho
+    int32_t *d_cov_flags = nullptr; int64_t cov_flags_cap = 0;    // P: info != 0 or tinfo != 0
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -360,6 +366,7 @@ int launch_mix_grad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_
 int launch_trend_vgrad(pmk_query *q, hipStream_t s);
 int launch_mix_vgrad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_cov(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s);
+int launch_cov_trend(pmk_query *q, hipStream_t s);
 int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
                              const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);

@@ -969,6 +969,22 @@ class DeviceQuery:
             ptr = C.byref(d)
         _lib.check(self.L.pmk_query_items_cov(self.h, ptr), "pmk_query_items_cov")
 
+    def items_cov_multi(self, theta=None):
+        """pmk_query_items_cov_multi: items_cov on the multi-output path, after items_multi / items_multi_fitted on this
+        plan.  Under the model's trend the blocks carry its term z_a . z_b (the universal-kriging covariance, whose diagonal
+        is the item variance of items_multi); without one they are those of items_cov bit for bit.  `theta` is the kernel
+        given to the items call, or (None) the model's own.  mix_cov, fetch_cov and item_covs serve the results.
+        Closure-carrying kernels raise TypeError before any device call."""
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            _refuse_closure_kernel(theta, "items_cov_multi")
+            d = theta.desc()
+            ptr = C.byref(d)
+        _lib.check(self.L.pmk_query_items_cov_multi(self.h, ptr), "pmk_query_items_cov_multi")
+
     def mix_cov(self, weight_theta):
         """pmk_query_mix_cov: the joint covariance of the whole batch under the blend of mix()"""
         _refuse_closure_kernel(weight_theta, "mix_cov")
@@ -1708,6 +1724,74 @@ def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws,
         if tuple(z.shape) != (int(n_draws), Nq):
             raise ValueError("z must have shape (%d, %d), not %s" % (int(n_draws), Nq, tuple(z.shape)))
     return Yq[None, :] + z @ L.T, jitter
+
+
+def _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, who):
+    """_cov_query on the multi-output path: the R blended means, the variances and the region blocks with the term of
+    the model's trend, on what fitmixtureGP_multi_ / fitmixtureGP_trend_ left resident"""
+    _refuse_closure_kernel(weight_theta, who)
+    theta = getattr(getattr(eta, "_model", None), "theta", None)
+    if theta is not None:
+        _refuse_closure_kernel(theta, who)
+    q = _patches_query(Xq, eta, root, radius, delta, who)
+    q.model._need(multi=True)
+    q.items_multi_fitted(True)
+    q.mix_multi(weight_theta)
+    q.items_cov_multi()
+    q.mix_cov(weight_theta)
+    return q
+
+
+def querymixtureGP_cov_multi(Xq, eta, root, levels, radius, delta, weight_theta):
+    """querymixtureGP_multi_patches with the joint posterior covariance of the batch -> (Yq [Nq, R], Vq, Cov [Nq, Nq]),
+    for the R columns of fitmixtureGP_multi_ or fitmixtureGP_trend_ (list-built and from_tree etas).  Under a trend Cov is
+    the universal-kriging covariance: every region's term carries z_j . z_k of the drift's uncertainty, and its diagonal
+    is the Vq the model predicts, up to rounding.  The covariance does not depend on the targets: the R columns are
+    independent fields with a common kernel and share Cov.  At most 16384 queries."""
+    q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, "querymixtureGP_cov_multi")
+    Yq, Vq = q.fetch_multi(q.model.R)
+    return Yq, Vq, q.fetch_cov()
+
+
+def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None):
+    """posterior draws of the R latent blended fields at Xq -> (draws [n_draws, Nq, R] as a torch device tensor, jitter).
+    The joint covariance of querymixtureGP_cov_multi is factored once (torch.linalg.cholesky_ex, the jitter ladder of
+    samplemixtureGP) and serves every column: draws[:, :, c] = Yq[:, c] + z[:, :, c] L^T with independent standard normals
+    per column.  z [n_draws, Nq, R]: the normals to use; otherwise they are drawn from `generator`.  A covariance that
+    holds NaN (a batch that blends a patch whose factorisation failed or whose trend is flagged) raises LinAlgError
+    before any factorisation."""
+    import torch
+
+    q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP_multi")
+    dev = torch.device("cuda", q.model.ctx.device)
+    Nq, R = q.Nq, int(q.model.R)
+    Cov = torch.empty((Nq, Nq), dtype=torch.float64, device=dev)
+    Yq = torch.empty((R, Nq), dtype=torch.float64, device=dev)          # column-major (Nq, R)
+    q.fetch_multi_into(Yq.T)
+    q.fetch_cov_into(Cov)
+    q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
+    if not bool(torch.isfinite(Cov).all()):
+        raise np.linalg.LinAlgError("samplemixtureGP_multi: the joint covariance holds NaN or Inf entries: a query of the "
+                                    "batch blends a patch whose factorisation failed (DeviceModel.info()) or whose trend "
+                                    "is flagged (DeviceModel.trend_info())")
+    scale = float(torch.trace(Cov)) / max(Nq, 1)
+    jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
+    while True:
+        L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
+        if int(info) == 0:
+            break
+        jitter = 2.0 ** -52 * scale if jitter == 0.0 else 10.0 * jitter
+        if not jitter <= 2.0 ** -26 * scale:
+            raise np.linalg.LinAlgError("samplemixtureGP_multi: the joint covariance is not positive definite with a "
+                                        "jitter of up to 2^-26 trace / Nq")
+    if z is None:
+        z = torch.randn((int(n_draws), Nq, R), dtype=torch.float64, device=dev, generator=generator)
+    else:
+        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
+        if tuple(z.shape) != (int(n_draws), Nq, R):
+            raise ValueError("z must have shape (%d, %d, %d), not %s" % (int(n_draws), Nq, R, tuple(z.shape)))
+    # column by column, each as samplemixtureGP takes its draws
+    return torch.stack([Yq[c][None, :] + z[:, :, c] @ L.T for c in range(R)], dim=2), jitter
 
 
 def querymixtureGP_multi_patches(Xq, eta, root, levels, radius, delta, weight_theta, variance=True):
