@@ -16,8 +16,9 @@ extern "C" {
 #endif
 
 /* C[I][J] (128 x 32, J contiguous: C[J + 32*I]) = sum_k MI[I + 128 k] MJ[J + 32 k],
- * k < K (K a multiple of 16), through the three forms of the wave-tile GEMM loop (gemm_nt, gemm_nt_indexed,
- * gemm_nt_sbase) of one wave; elements on which they disagree come back as NaN.  Host buffers. */
+ * k < K (K a multiple of 16), through the four forms of the wave-tile GEMM loop (gemm_nt, gemm_nt_indexed,
+ * gemm_nt_sbase, gemm_nt_buf -- the last also with a J ring of 8 k-steps where K is a multiple of 32) of one wave;
+ * elements on which they disagree come back as NaN.  Host buffers. */
 int pmk_selftest_gemm(pmk_ctx *ctx, int K, const double *MI, const double *MJ, double *C);
 /* T (128 x 32, T[J + 32*I]) <- -L^-1 T through tri_solve_inplace (operands staged in LDS) AND tri_solve_global (operands
  * prefetched from global memory); elements on which the two disagree come back as NaN.  L is 128 x 128 column-major
@@ -45,6 +46,16 @@ int pmk_test_model_packed(pmk_model *model, int64_t patch, int what, int64_t *ld
 /* the device addresses of the model's slabs, coordinates and weights as integers (tests of pmk_model_reserve: a call
  * with nothing to grow must not move the model, one that grows a patch moves all of it); never dereferenced */
 int pmk_test_model_buffers(pmk_model *model, int64_t *slabs, int64_t *points, int64_t *weights);
+
+/* 1 if the buffer-load form of the wave-tile GEMM can address an operand of K columns with leading dimension ld
+ * (elements of elem_size bytes, J ring of pfj k-steps) with its 32-bit offsets: (K + 4 pfj) ld elem_size < 2^31; else 0.
+ * Pure: needs no device. */
+int pmk_test_gemm_buf_extent_ok(int64_t K, int64_t ld, int pfj, int elem_size);
+
+/* the loop forms that PMK_STEP_GEMM=auto gives the factorisation step launch with G block rows below the diagonal at
+ * block column k: 0 = pointer form (gemm_nt), 1 = buffer-load form (gemm_nt_buf).  A function of its four arguments
+ * alone.  Pure: needs no device. */
+int pmk_test_step_gemm_rule(int G, int k, int f32, int fused);
 
 #ifdef __cplusplus
 }

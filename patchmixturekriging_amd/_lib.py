@@ -206,6 +206,8 @@ SIGNATURES = {
     "pmk_test_model_set_split": (C.c_int, [_vp, C.c_int]),
     "pmk_test_model_packed": (C.c_int, [_vp, C.c_int64, C.c_int, _ip, _dp]),
     "pmk_test_model_buffers": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "pmk_test_gemm_buf_extent_ok": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "pmk_test_step_gemm_rule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
 }
 
 

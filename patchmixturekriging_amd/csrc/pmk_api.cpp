@@ -731,6 +731,14 @@ int pmk_test_model_buffers(pmk_model *m, int64_t *slabs, int64_t *points, int64_
     return 0;
 }
 
+/* include/pmk_test.h: the two pure functions behind the loop form of the factorisation steps' GEMMs */
+int pmk_test_gemm_buf_extent_ok(int64_t K, int64_t ld, int pfj, int elem_size)
+{
+    return gemm_buf_extent_ok(K, ld, pfj, elem_size) ? 1 : 0;
+}
+
+int pmk_test_step_gemm_rule(int G, int k, int f32, int fused) { return step_gemm_rule(G, k, f32 != 0, fused != 0); }
+
 /* include/pmk_test.h: the packed buffers of one patch, padding rows included */
 int pmk_test_model_packed(pmk_model *m, int64_t patch, int what, int64_t *ld, double *out)
 {
@@ -745,6 +753,19 @@ int pmk_test_model_packed(pmk_model *m, int64_t patch, int what, int64_t *ld, do
     const int64_t off = what == 0 ? d.xoff : what == 3 ? d.yoff * PMK_MAX_OUTPUTS : d.yoff;
     const int64_t count = (int64_t)d.ld * (what == 0 ? m->D : what == 3 ? PMK_MAX_OUTPUTS : 1);
     return download_real_2d(m, out, count, src, off, count, count, 1, m->ctx->stream);
+}
+
+// PMK_STEP_GEMM: the loop form of the factorisation steps' GEMMs (pmk_chol.hip).  ptr | buf force one form in every
+// launch (A/B runs, tests); auto, the default, asks step_gemm_rule per launch.  Both forms give the same bits.  Any other
+// value is an error (-2): a misspelt arm of an A/B run must not quietly measure the default.
+static int step_gemm_env(int *form)
+{
+    const char *e = std::getenv("PMK_STEP_GEMM");
+    if (!e || !*e || !std::strcmp(e, "auto")) *form = -1;
+    else if (!std::strcmp(e, "ptr")) *form = pmk::STEP_GEMM_PTR;
+    else if (!std::strcmp(e, "buf")) *form = pmk::STEP_GEMM_BUF;
+    else { set_error("PMK_STEP_GEMM=%s: expected ptr, buf or auto", e); return -2; }
+    return 0;
 }
 
 // The three timed stages of a fit: kernel matrix (th as the launchers take it, m->fuse_k1 decided by the caller),
@@ -787,6 +808,7 @@ int pmk_model_fit(pmk_model *m, const pmk_kernel_desc *th, double sigma2)
     const char *fe = std::getenv("PMK_FUSE_K1");
     const bool fuse_env = !(fe && std::atoi(fe) == 0);
     m->fuse_k1 = fuse_env && th->family == PMK_SPLINE34 && (m->D == 2 || m->D == 3) && !m->split_mode && m->max_nt >= 2;
+    if (int rc = step_gemm_env(&m->step_gemm)) return rc;
     if (int rc = fit_stages(m, th, sigma2)) return rc;
     c->toc("fit");
     m->fitted = true;
@@ -838,6 +860,7 @@ int pmk_model_fit_patches(pmk_model *m, const pmk_kernel_desc *ths, const double
     c->tic("fit");
     // always the whole lower triangle: the fused build evaluates tiles inside the factorisation, which knows one theta
     m->fuse_k1 = false;
+    if ((rc = step_gemm_env(&m->step_gemm))) return rc;
     if ((rc = fit_stages(m, nullptr, 0.0))) return rc;
     c->toc("fit");
     m->fitted = true;

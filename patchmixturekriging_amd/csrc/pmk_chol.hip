@@ -46,6 +46,17 @@ constexpr int POTRF_END = POTRF_BAD + 2;
 constexpr int PARTIAL_TILE = TILE * TILE / 2;      // a 128 x 128 partial product tile in real2 units
 static_assert(POTRF_END <= TRI_LDS_DOUBLES, "potrf scratch must fit into the TRSM operand array");
 
+// One GEMM site of the step kernel: the pointer form gemm_nt or (BUF) the buffer-load form gemm_nt_buf -- the same MFMAs
+// in the same order, the same bits.  Which one a launch takes: STEP_GEMM_* / step_gemm_rule, pmk_internal.h.
+// K is a positive multiple of TILE at every site.
+template <bool BUF, int NPI, int NPJ, int PFI, int PFJ = PFI>
+__device__ __forceinline__ void step_gemm(WaveTile<NPI, NPJ> &t, const real *opI, const real *opJ, int64_t ld, int K, int lane)
+{
+    static_assert(TILE % (4 * PFJ) == 0, "the rings consume K in groups of 4 PFJ columns");
+    if (BUF) gemm_nt_buf<NPI, NPJ, PFI, PFJ>(t, opI, ld, opJ, ld, K, lane);
+    else gemm_nt<NPI, NPJ, PFI, PFJ>(t, opI, ld, opJ, ld, K, lane);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Stores of the chained solves (solve_chain_kernel): a solution block that another workgroup of the SAME launch will
 // read is written through (sc1: the bytes leave the XCD's L2 at once), so the hand-off needs no release fence -- every
@@ -234,7 +245,8 @@ __global__ __launch_bounds__(256, 2) void chol_first_kernel(const PatchDesc *__r
 // kern_eval as K1: the same bits, without the write of the tile by K1 and its read here (the strictly lower 128 x 128
 // tiles are 7/8 of a 2000-point patch's kernel matrix).  Padding rows carry coordinates of 1e300, where the compact
 // profile is exactly 0 (a padded row never meets a padded column below the diagonal tiles).
-template <int SPLIT, int KD = 0>
+// BUF: the deep product runs in the buffer-load form (step_gemm).
+template <int SPLIT, int KD = 0, bool BUF = false>
 __device__ __forceinline__ void block_row_update(const PatchDesc &pd, real *__restrict__ S, const real *__restrict__ ninv_p,
                                                  int k, int row, real *lds, const real2_t *__restrict__ pt, int nsplit,
                                                  const real *__restrict__ xs = nullptr, const pmk_kernel_desc *th = nullptr)
@@ -330,7 +342,7 @@ __device__ __forceinline__ void block_row_update(const PatchDesc &pd, real *__re
                     acc.f[fi][1][q] += v[1];
                 }
     } else if (k > 0) {
-        gemm_nt<4, 1, PF_CHOL, PFJ_CHOL>(acc, S + c0, ld, S + r0, ld, k * TILE, lane);
+        step_gemm<BUF, 4, 1, PF_CHOL, PFJ_CHOL>(acc, S + c0, S + r0, ld, k * TILE, lane);
     }
     // L[rows, k]^T = L[kk]^-1 T^T = -L[kk]^-1 (-T)^T : exactly what the block substitution returns
     tri_solve_inplace<1>(acc, lds, lane);
@@ -353,7 +365,7 @@ __device__ __forceinline__ void block_row_update(const PatchDesc &pd, real *__re
 // Block columns 0 .. nb - 1 are applied: nb = k + 1 before the potrf (lookahead_potrf), nb = 0 for the split path's fold
 // of the partial tiles alone (chol_step_kernel<1>, block column k is not made yet).  rhs_src = y_{k+1}; the right-hand
 // side is reduced block column by block column, and that order is part of the bits of z.
-template <int SPLIT>
+template <int SPLIT, bool BUF = false>
 __device__ __forceinline__ void lookahead_update(const PatchDesc &pd, real *__restrict__ S,
                                                  const real *rhs_src, const real *z_p, int k, real *lds,
                                                  const real2_t *__restrict__ pt, int nsplit, int nb)
@@ -417,7 +429,7 @@ __device__ __forceinline__ void lookahead_update(const PatchDesc &pd, real *__re
                     acc.f[fi][2 * pj][q] = -a[0];
                     acc.f[fi][2 * pj + 1][q] = -a[1];
                 }
-        if (K2 > 0) gemm_nt<2, 2, PF_DIAG>(acc, S + t0 + 64 * g, ld, S + t0 + 64 * h, ld, K2, lane);
+        if (K2 > 0) step_gemm<BUF, 2, 2, PF_DIAG>(acc, S + t0 + 64 * g, S + t0 + 64 * h, ld, K2, lane);
 #pragma unroll
         for (int fi = 0; fi < 4; ++fi)
 #pragma unroll
@@ -456,13 +468,13 @@ __device__ __forceinline__ void lookahead_update(const PatchDesc &pd, real *__re
     }
 }
 
-template <int SPLIT>
+template <int SPLIT, bool BUF = false>
 __device__ __forceinline__ void lookahead_potrf(const PatchDesc &pd, real *__restrict__ S, real *__restrict__ ninv_p,
                                                 const real *__restrict__ y_p, real *__restrict__ z_p,
                                                 int32_t *__restrict__ info_p, int k, real *lds,
                                                 const real2_t *__restrict__ pt, int nsplit)
 {
-    lookahead_update<SPLIT>(pd, S, y_p + (int64_t)(k + 1) * TILE, z_p, k, lds, pt, nsplit, k + 1);
+    lookahead_update<SPLIT, BUF>(pd, S, y_p + (int64_t)(k + 1) * TILE, z_p, k, lds, pt, nsplit, k + 1);
     __syncthreads();
     const int64_t t0 = (int64_t)(k + 1) * TILE;
     tile_potrf(S + t0 + t0 * pd.ld, pd.ld, lds, ninv_p + (int64_t)(k + 1) * (4 * SB * SB), z_p + t0, info_p, k + 1);
@@ -492,8 +504,10 @@ __device__ __forceinline__ void step_slot(int nslots, int G, int &slot, int &bx)
 // were done by chol_partial_kernel, SPLIT-way split along K, and left as partial tiles; this kernel then adds them up,
 // applies block column k itself (128 deep) and carries on as above -- except that the forward-solve right-hand side is
 // not carried along (z comes from the separate solve sweeps of that path).
+// BUF: the block-row GEMM and the look-ahead GEMM run in the buffer-load form; chosen per launch (step_gemm_rule).  The
+// split path keeps the pointer form.
 // ---------------------------------------------------------------------------------------------
-template <int SPLIT, int KD = 0>
+template <int SPLIT, int KD = 0, bool BUF = false>
 __global__ __launch_bounds__(256, 2) void chol_step_kernel(const PatchDesc *__restrict__ descs,
                                                            const int32_t *__restrict__ order, int nactive, int G,
                                                            int launch, int max_nt, real *__restrict__ A,
@@ -551,9 +565,9 @@ __global__ __launch_bounds__(256, 2) void chol_step_kernel(const PatchDesc *__re
     }
 #endif
     PMK_STAMP(2);
-    block_row_update<SPLIT, KD>(pd, S, ninv + pd.ioff, k, k + 1 + bx, lds,
-                                SPLIT ? partial + (((int64_t)slot * (G + 1) + bx) * nsplit) * PARTIAL_TILE : nullptr, nsplit,
-                                KD ? x + pd.xoff : nullptr, &th);
+    block_row_update<SPLIT, KD, BUF>(pd, S, ninv + pd.ioff, k, k + 1 + bx, lds,
+                                     SPLIT ? partial + (((int64_t)slot * (G + 1) + bx) * nsplit) * PARTIAL_TILE : nullptr, nsplit,
+                                     KD ? x + pd.xoff : nullptr, &th);
     PMK_STAMP(3);
 #ifdef PMK_TRACE
     if (launch == PMK_TRACE && tid == 0 && blockIdx.x < TRACE_MAX_WG)      // shader cycles of wave 0's block-row phase
@@ -565,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void chol_step_kernel(const PatchDesc *__re
     // ================= critical workgroup: look-ahead + potrf of diagonal tile k + 1 =================
     __syncthreads();
     PMK_STAMP(4);
-    lookahead_potrf<SPLIT>(pd, S, ninv + pd.ioff, y + pd.yoff, z + pd.yoff, info + pid, k, lds,
+    lookahead_potrf<SPLIT, BUF>(pd, S, ninv + pd.ioff, y + pd.yoff, z + pd.yoff, info + pid, k, lds,
                            SPLIT ? partial + (((int64_t)slot * (G + 1) + G) * nsplit) * PARTIAL_TILE : nullptr, nsplit);
     PMK_STAMP(5);
     if (probe) {
@@ -1094,6 +1108,10 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
     if (half_tiles)
         if (int rc = reserve_split(m, 2 * sizeof(real2_t) * (size_t)PARTIAL_TILE * half_tiles, 0)) return rc;
     struct Pending { int n, G, nsplit; const real2_t *buf; int l; } pend = {0, 0, 1, nullptr, -1};
+    // the buffer form of the step GEMMs addresses a slab with 32-bit offsets: every patch's deepest product must fit
+    bool buf_ok = true;
+    for (const PatchDesc &d : m->desc)
+        buf_ok = buf_ok && gemm_buf_extent_ok((int64_t)d.nt * TILE, d.ld, std::max(PFJ_CHOL, PF_DIAG), (int)sizeof(real));
     // a potrf-only launch (no split step follows the one that left it).  Only the call after the loop ever finds a pending
     // tile: nsplit_of(l, max_nt - l - 1) does not decrease with l, so no batched step follows a split one and the call
     // inside the loop is a no-op (tests/test_fit_schedule_model.py checks max_nt <= 160, P <= 64).
@@ -1134,15 +1152,25 @@ int launch_cholesky(pmk_model *m, hipStream_t s, int64_t p0, int64_t np)
                                                            // tiles are folded in by the step launch above: none left)
         } else {
             if (int rc = flush_pending()) return rc;
-#define PMK_STEP(KD_)                                                                                                        \
-            hipLaunchKernelGGL((chol_step_kernel<0, KD_>), dim3(grid), dim3(256), 0, s, m->d_desc, m->d_order, nactive, G, l,  \
+#define PMK_STEP_F(KD_, F_)                                                                                                  \
+            hipLaunchKernelGGL((chol_step_kernel<0, KD_, F_>), dim3(grid), dim3(256), 0, s, m->d_desc, m->d_order, nactive, G, l, \
                                m->max_nt, (real *)m->d_a, (real *)m->d_inv, (const real *)m->d_y, (real *)m->d_z, m->d_info,  \
                                (const real2_t *)nullptr, 1, m->ctx->d_clk, (const real *)m->d_x, m->th, 0)
+            // every launch runs the one instantiation of its form: no launch carries a loop it does not use
+#define PMK_STEP(KD_)                                                                                                        \
+            do {                                                                                                             \
+                if (form == STEP_GEMM_BUF) PMK_STEP_F(KD_, true);                                                            \
+                else PMK_STEP_F(KD_, false);                                                                                 \
+            } while (0)
+            const bool fused = m->fuse_k1 && (m->D == 2 || m->D == 3);
+            const int form = !buf_ok ? STEP_GEMM_PTR
+                             : m->step_gemm >= 0 ? m->step_gemm : step_gemm_rule(G, l, sizeof(real) == 4, fused);
             // fused kernel-matrix build (pmk_model_fit decides): the strictly lower tiles are evaluated at their first use
             if (m->fuse_k1 && m->D == 2) PMK_STEP(2);
             else if (m->fuse_k1 && m->D == 3) PMK_STEP(3);
             else PMK_STEP(0);
 #undef PMK_STEP
+#undef PMK_STEP_F
         }
         if (int rc = ev_end(l)) return rc;
     }

@@ -21,6 +21,35 @@ constexpr int TR_RP = PMK_MAX_OUTPUTS;        // columns of a row of the target 
 // holds two columns, a strip eight waves: 128 / 80 / 64 / 48 at D = 1 / 2 / 3 / 4
 constexpr int vgrad_strip_items(int D) { return 8 * 2 * (16 / (D + 1)); }
 
+// Can the buffer-load form of the wave-tile GEMM (pmk_mfma.h: gemm_nt_buf) address an operand of K columns with leading
+// dimension ld?  Its offsets are 32-bit and signed, and the scalar column offset runs up to pfj k-steps (4 pfj columns)
+// past K before the loop ends.  Where this does not hold (single problems with slabs of 2 GiB and more) the caller
+// takes gemm_nt.
+constexpr bool gemm_buf_extent_ok(int64_t K, int64_t ld, int pfj, int elem_size)
+{
+    return K > 0 && ld > 0 && pfj > 0 && elem_size > 0 &&
+           (K + 4 * (int64_t)pfj) <= (((int64_t)1 << 31) - 1) / (ld * (int64_t)elem_size);
+}
+
+// Loop form of the step kernel's GEMMs (pmk_chol.hip: block-row product and look-ahead), one per launch.
+constexpr int STEP_GEMM_PTR = 0;        // gemm_nt
+constexpr int STEP_GEMM_BUF = 1;        // gemm_nt_buf
+// The rule of PMK_STEP_GEMM=auto for the step launch that has G block rows below the diagonal and whose largest patches
+// are at block column k, for the element type and the fused / unfused kernel-matrix build: a function of these four
+// alone -- not of the number of patches or of their tile count.
+//   fused build  -> buffer form in every launch,   unfused build -> pointer form.
+// Measured per launch, 5 runs an arm against the parent build, alternating (profiles/step_gemm_forms.txt): with the
+// fused build the buffer form everywhere takes 1-3 % off the launches that the deep product dominates and 3-4 % off the
+// last two -- step launches 13.06-13.26 -> 12.87-12.95 ms at 16 tiles fp64, 7.24-7.28 -> 6.99-7.07 ms in fp32,
+// 3.86-3.91 -> 3.78-3.83 ms at 10 tiles, neutral at 24 tiles (22.17-22.28 -> 22.02-22.29 ms).  Where the tiles are
+// loaded instead of evaluated it loses (12.64-12.68 -> 12.70-12.76 ms).  Single launches move by 80-130 us with the form
+// in either direction and not reproducibly from box to box, so the rule does not follow single launches; G and k are
+// arguments because the choice is made per launch, and today the answer is the same for all of them.
+constexpr int step_gemm_rule(int G, int k, bool f32, bool fused)
+{
+    return (void)G, (void)k, (void)f32, fused ? STEP_GEMM_BUF : STEP_GEMM_PTR;
+}
+
 void set_error(const char *fmt, ...);
 
 #define PMK_HIP(expr)                                                                        \
@@ -138,6 +167,7 @@ struct pmk_model {
     // split path (few, large patches: the deep products of a step are cut along K over several workgroups and the two
     // triangular solves run block by block over many workgroups): chosen at creation from P and the tile counts
     bool split_mode = false;
+    int step_gemm = -1;                 // loop form of the step kernel's GEMMs: -1 by rule (step_gemm_rule), else STEP_GEMM_* forced in every launch
     bool fuse_k1 = false;               // this fit evaluates the strictly lower kernel-matrix tiles inside the factorisation
     void *d_partial = nullptr; size_t partial_bytes = 0;      // partial product tiles of one step
     void *d_solve_part = nullptr; size_t solve_bytes = 0;     // partial matrix-vector products of one solve block

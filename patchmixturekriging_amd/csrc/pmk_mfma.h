@@ -60,7 +60,8 @@ struct WaveTile {
 //
 // OVER-READ: the rings are refilled without a bounds test, so the routine LOADS (and never uses) up to PFI k-steps of
 // the I operand and PFJ k-steps of the J operand past K.  Every caller passes operands that lie inside a padded patch
-// slab / strip with at least that many columns (rows) behind K.
+// slab / strip with at least that many columns (rows) behind K.  (gemm_nt_buf below has no such precondition; this
+// routine is also its fallback for operands whose extent reaches 2 GiB: gemm_buf_extent_ok, pmk_internal.h.)
 //
 // Waits.  The loop relies on counted waits (s_waitcnt vmcnt(N): the loads of the last PF-1 k-steps stay in flight).
 // The wait at the loop head serves the entry from the prologue as well as the back edge, so the prologue must issue
@@ -245,6 +246,104 @@ __device__ __forceinline__ void gemm_nt(WaveTile<NPI, NPJ> &t, const real *opI, 
     // the ring loads as well.  For callers under register pressure (prediction); it costs code size elsewhere.
     if (PEEL) pass();
     for (int k0 = PEEL ? 4 * PFJ : 0; k0 < K; k0 += 4 * PFJ) pass();
+}
+
+// Buffer-load form of gemm_nt: the same k order, the same MFMAs into the same accumulators (bit-identical), with every
+// ring address given as
+//     (resource descriptor of the operand: four scalar registers)  +  (one 32-bit byte offset per lane, computed once)
+//     +  (the byte offset of the k-step: one scalar register, advanced on the scalar ALU),
+// so the loop body holds MFMAs, buffer loads and scalar adds -- none of the 64-bit vector address updates of gemm_nt,
+// which are not hidden behind the MFMAs on gfx950 (tools/gemm_probe.hip: 96.2 % of the fp64 MFMA peak with two waves
+// per SIMD against 94.0 %; a wave alone 94.0 % against 91.7 %).  The loads are builtins: the compiler counts vmcnt
+// itself, so unlike gemm_nt_sbase the routine is safe where the compiler spills.
+// Nothing behind K is read: past the end the refills fetch the last k-step again (a scalar minimum on the k-step
+// offset; into registers nobody uses any more), and each descriptor carries the extent of its operand (num_records =
+// the bytes up to the end of the last column the MFMAs consume) for the hardware's range check, which answers an
+// out-of-range load with zeros instead of touching memory.
+// Requirements: opI, opJ, ldI, ldJ, K wave-uniform (they are moved to scalar registers here: a descriptor in vector
+// registers would be waterfalled); K a positive multiple of 4 PFJ; gemm_buf_extent_ok(K, ld, PFJ, sizeof(real)) for
+// both operands (pmk_internal.h).
+template <int NPI, int NPJ, int PFI, int PFJ = PFI, int NACT = NPI>
+__device__ __forceinline__ void gemm_nt_buf(WaveTile<NPI, NPJ> &t, const real *opI, int64_t ldI, const real *opJ, int64_t ldJ,
+                                            int K, int lane)
+{
+    static_assert(PFJ % PFI == 0, "the J ring depth must be a multiple of the I ring depth");
+    static_assert(NACT >= 1 && NACT <= NPI, "active pairs");
+    constexpr int ES = (int)sizeof(real);
+    constexpr int AUX_STREAM = 2;                  // nt: the J operand is this wave's own stream (see gemm_nt)
+    constexpr int RSRC_RAW32 = 0x00020000;         // descriptor word 3: raw buffer, 32-bit data format, no swizzle
+    real2_t ra[PFI][NACT], rb[PFJ][NPJ];
+    const int uI = __builtin_amdgcn_readfirstlane((int)ldI), uJ = __builtin_amdgcn_readfirstlane((int)ldJ);
+    const int uK = __builtin_amdgcn_readfirstlane(K);
+    const __amdgpu_buffer_rsrc_t rI =
+        __builtin_amdgcn_make_buffer_rsrc((void *)uniform_ptr(opI), 0, ((uK - 1) * uI + 32 * NACT) * ES, RSRC_RAW32);
+    const __amdgpu_buffer_rsrc_t rJ =
+        __builtin_amdgcn_make_buffer_rsrc((void *)uniform_ptr(opJ), 0, ((uK - 1) * uJ + 32 * NPJ) * ES, RSRC_RAW32);
+    // the lane's element of a k-step: indices 2 rho, 2 rho + 1 at column (lane >> 4)
+    const int vI = (2 * (lane & 15) + (lane >> 4) * uI) * ES;
+    const int vJ = (2 * (lane & 15) + (lane >> 4) * uJ) * ES;
+    const int sI = 4 * uI * ES, sJ = 4 * uJ * ES;
+    const int endI = (uK / 4 - 1) * sI, endJ = (uK / 4 - 1) * sJ;      // the last k-step
+    int oI = 0, oJ = 0;                            // scalar byte offsets of the next k-step to load
+    int cI = 0, cJ = 0;                            // ... clamped to the last k-step
+    auto load_I = [&](int pi) {
+#ifdef PMK_REAL_F32
+        return __builtin_bit_cast(real2_t, __builtin_amdgcn_raw_buffer_load_b64(rI, vI + 32 * ES * pi, cI, 0));
+#else
+        return __builtin_bit_cast(real2_t, __builtin_amdgcn_raw_buffer_load_b128(rI, vI + 32 * ES * pi, cI, 0));
+#endif
+    };
+    auto load_J = [&](int pj) {
+#ifdef PMK_REAL_F32
+        return __builtin_bit_cast(real2_t, __builtin_amdgcn_raw_buffer_load_b64(rJ, vJ + 32 * ES * pj, cJ, AUX_STREAM));
+#else
+        return __builtin_bit_cast(real2_t, __builtin_amdgcn_raw_buffer_load_b128(rJ, vJ + 32 * ES * pj, cJ, AUX_STREAM));
+#endif
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    // the prologue issues its loads in the order the loop consumes them, pinned (see gemm_nt: the wait at the loop head)
+#pragma unroll
+    for (int s = 0; s < PFJ; ++s) {
+        if (s < PFI) {
+#pragma unroll
+            for (int pi = 0; pi < NACT; ++pi) ra[s][pi] = load_I(pi);
+            oI += sI;
+            cI = oI < endI ? oI : endI;
+        }
+#pragma unroll
+        for (int pj = 0; pj < NPJ; ++pj) rb[s][pj] = load_J(pj);
+        oJ += sJ;
+        cJ = oJ < endJ ? oJ : endJ;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    for (int k0 = 0; k0 < uK; k0 += 4 * PFJ) {
+#pragma unroll
+        for (int s = 0; s < PFJ; ++s) {
+            const int si = s % PFI;
+#pragma unroll
+            for (int pi = 0; pi < NACT; ++pi) {
+#pragma unroll
+                for (int ei = 0; ei < 2; ++ei)
+#pragma unroll
+                    for (int pj = 0; pj < NPJ; ++pj)
+#pragma unroll
+                        for (int ej = 0; ej < 2; ++ej)
+                            t.f[2 * pi + ei][2 * pj + ej] =
+                                mfma_real(ra[si][pi][ei], rb[s][pj][ej], t.f[2 * pi + ei][2 * pj + ej]);
+                // each I slot is refilled right behind the MFMAs that consumed it
+                ra[si][pi] = load_I(pi);
+                if (pi == NACT - 1) {
+#pragma unroll
+                    for (int pj = 0; pj < NPJ; ++pj) rb[s][pj] = load_J(pj);
+                }
+                __builtin_amdgcn_sched_barrier(0);      // see gemm_nt
+            }
+            oI += sI;
+            oJ += sJ;
+            cI = oI < endI ? oI : endI;
+            cJ = oJ < endJ ? oJ : endJ;
+        }
+    }
 }
 
 // The same product with every ring address recomputed from the k index (clamped at the end: no over-read).  Costs a

@@ -32,6 +32,30 @@ __global__ __launch_bounds__(64) void selftest_gemm_kernel(int K, const double *
             }
 }
 
+// the buffer-load form against what selftest_gemm_kernel left in C (the common value of the other three forms, or NaN).
+// A kernel of its own: a fourth accumulator tile beside the asm form would only add spills around hand-written waits.
+__global__ __launch_bounds__(64) void selftest_gemm_buf_kernel(int K, const double *MI, const double *MJ, double *C)
+{
+    const int lane = threadIdx.x;
+    WaveTile<4, 1> w, w2;
+    w.zero();
+    w2.zero();
+    gemm_nt_buf<4, 1, 4>(w, MI, 128, MJ, 32, K, lane);
+    // a J ring deeper than the I ring (K in groups of 32 columns): the same k order, so the same bits
+    const bool deep = K % 32 == 0;
+    if (deep) gemm_nt_buf<4, 1, 4, 8>(w2, MI, 128, MJ, 32, K, lane);
+#pragma unroll
+    for (int fi = 0; fi < 8; ++fi)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int fj = 0; fj < 2; ++fj) {
+                const int I = 32 * (fi >> 1) + 2 * ((lane >> 4) + 4 * q) + (fi & 1);
+                const int J = 32 * (fj >> 1) + 2 * (lane & 15) + (fj & 1);
+                if (!(w.f[fi][fj][q] == C[J + 32 * I]) || (deep && !(w2.f[fi][fj][q] == w.f[fi][fj][q]))) C[J + 32 * I] = __builtin_nan("");
+            }
+}
+
 __global__ __launch_bounds__(64) void selftest_trisolve_kernel(const double *L, const double *ninv, const double *Tin, double *Tout)
 {
     const int lane = threadIdx.x;
@@ -103,6 +127,8 @@ int pmk_selftest_gemm(pmk_ctx *ctx, int K, const double *MI, const double *MJ, d
     PMK_HIP(hipMemcpy(dI, MI, sizeof(double) * 128 * K, hipMemcpyHostToDevice));
     PMK_HIP(hipMemcpy(dJ, MJ, sizeof(double) * 32 * K, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(selftest_gemm_kernel, dim3(1), dim3(64), 0, ctx->stream, K, dI, dJ, dC);
+    // the same (padded) operands: the buffer form reads nothing behind K, which a value cannot show either way
+    hipLaunchKernelGGL(selftest_gemm_buf_kernel, dim3(1), dim3(64), 0, ctx->stream, K, dI, dJ, dC);
     PMK_HIP(hipGetLastError());
     PMK_HIP(hipStreamSynchronize(ctx->stream));
     PMK_HIP(hipMemcpy(C, dC, sizeof(double) * 128 * 32, hipMemcpyDeviceToHost));
