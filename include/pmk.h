@@ -83,7 +83,7 @@ int  pmk_ctx_set_stream_null(pmk_ctx *ctx);
 int  pmk_ctx_synchronize(pmk_ctx *ctx);
 void pmk_ctx_destroy(pmk_ctx *ctx);
 /* elapsed ms of the most recent staged call's named stage ("kernel_matrix", "cholesky",
- * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad", "items_cov", "mix_cov", "cov_trend"); enabled by pmk_ctx_enable_timers(ctx, 1) */
+ * "solve", "plan", "items", "mix", "solve_multi", "items_multi", "mix_multi", "loo", "evidence", "trend_gls", "trend_items", "loo_items", "loo_items_multi", "items_grad", "mix_grad", "items_vgrad", "mix_vgrad", "items_cov", "mix_cov", "cov_trend", "factor_cov", "draw"); enabled by pmk_ctx_enable_timers(ctx, 1) */
 int  pmk_ctx_enable_timers(pmk_ctx *ctx, int on);
 int  pmk_ctx_timer_ms(pmk_ctx *ctx, const char *stage, double *ms);
 /* shader clock (GHz) that workgroups 0..7 (one per XCD) saw over their lifetime in the factorisation step launches of
@@ -648,6 +648,51 @@ int  pmk_query_items_cov_multi(pmk_query *q, const pmk_kernel_desc *th);
 int  pmk_predict_mixture_cov_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                           double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *Cov,
                                           int64_t ldc);
+
+/* ---- posterior draws from the region blocks: no Nq x Nq covariance ---------------------------------------------------
+ * The patches are independent GPs, so with S_r = L_r L_r^T the region blocks of pmk_query_items_cov(_multi),
+ *   E_s(x_j) = sum over the items i of j:  wn_i (L_{r(i)} zeta_{r(i),s})[a(i)],   zeta independent standard normals,
+ * is a zero-mean joint draw of the blend whose covariance is the entry pmk_query_mix_cov computes, the cross term of a
+ * query that holds two items of one region included.  Cost: sum m_r^3 / 3 flop and 8 sum m_r^2 bytes instead of
+ * Nq^3 / 3 and 16 Nq^2: the batch is limited by the items per region and by memory, not by PMK_COV_MAX_QUERIES.
+ * Double only; serves fp64 and fp32 models (the blocks are doubles in both).  A region's factor is a function of its
+ * block and its jitter alone: the same bits in every run, whatever other regions the batch holds.  Stage timers
+ * "factor_cov" and "draw".  Memory, owned by the query object, grow only: the factors padded to tiles of 32 rows (about
+ * 8 sum m_r^2 bytes), a total_items x (draw chunk) workspace of at most 256 MiB, 68 bytes per patch, 8 bytes per tile row,
+ * and for host pointers a chunk of z and of E.  Out of scope: the sharded and all-gather exchanges, random numbers inside
+ * the library, a one-shot call (the length of z depends on the plan). */
+/* the block stage of pmk_query_items_cov (multi = 0) or pmk_query_items_cov_multi (multi != 0) without the refusal above
+ * PMK_COV_MAX_QUERIES: the same checks, kernels and bits.  pmk_query_get_items_cov serves the blocks; pmk_query_mix_cov
+ * refuses them with -5 on a batch above the limit. */
+int  pmk_query_items_cov_blocks(pmk_query *q, const pmk_kernel_desc *th, int multi);
+/* enqueues the Cholesky factorisation of every region block of the current plan into a second buffer (the blocks stay):
+ * block r is factored as S_r + rel[r] (trace S_r / m_r) I, the trace summed in one fixed order.  rel: P host values, NULL
+ * for zeros.  A region that an earlier call on the same blocks factored (status 0) with the same rel[r] is not factored
+ * again and keeps its bits: a retry costs the regions that failed.  New blocks, new items under a trend and a new plan
+ * discard the factors.  Serves a query made by pmk_query_create_items too.  -1: no plan; -2: no blocks on this plan, or
+ * a negative or non-finite rel[r]; -100: an allocation failed (the text gives the bytes asked for). */
+int  pmk_query_factor_cov(pmk_query *q, const double *rel);
+/* blocks.  finfo[r]: 0 the block was factored (or is empty); k in 1 .. m_r: pivot k is NaN or <= 0 to rounding, that is
+ * not above 2^-50 (S_kk + jitter), what two copies of one item leave (the leading-minor convention of pmk_model_info),
+ * the factor of that region is unusable; -1: the patch is failed or its trend is flagged
+ * (what pmk_query_mix_cov reads as bad), the block was not factored.  jitter[r]: the absolute value added to the
+ * diagonal.  P entries each, either may be NULL.  Returns 1 if any finfo is non-zero, else 0; -1: no plan; -2: before
+ * pmk_query_factor_cov. */
+int  pmk_query_factor_info(pmk_query *q, int32_t *finfo, double *jitter);
+/* blocks; L_r, m x m column-major with ldl >= m, the strict upper triangle zero; rows in the order of
+ * pmk_query_get_items_cov.  m and L may be NULL.  Refusals as pmk_query_get_items_cov, and -2 before a factorisation. */
+int  pmk_query_get_items_cov_factor(pmk_query *q, int64_t region, int64_t *m, double *L, int64_t ldl);
+/* E[j + lde s] = the zero-mean part of draw s at query j (the caller adds Yq; for R target columns, column c to draws
+ * made from independent z), s < n_draws, lde >= Nq.  z[p + ldz s]: the normal of the sorted item at position p (region r
+ * owns the positions roff[r] .. roff[r + 1] - 1 of pmk_query_region_offsets, in the row order of pmk_query_get_items_cov),
+ * ldz >= total_items.  z and E are host or device pointers, classified by the runtime as pmk_query_create classifies Xq:
+ * with device pointers the call only enqueues, with a host pointer it blocks.  The sum over a query's items is one chain
+ * of fused multiply-adds in the item order and with the weights of pmk_query_mix.  A query that blends an item of a region
+ * with finfo != 0 is NaN in every draw; the others keep their bits.  n_draws = 0 returns 0.  -1: no plan; -2: before
+ * pmk_query_factor_cov, a query of explicit items, a Brownian-bridge or unknown weight kernel, z or E NULL; -4: a leading
+ * dimension is too small; -100: an allocation failed (the text gives the bytes asked for). */
+int  pmk_query_draw(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t n_draws, const double *z, int64_t ldz, double *E,
+                    int64_t lde);
 
 /* ---- appending observations to a fitted model in place: the border of the Cholesky factor ---------------------------
  * A patch's buffers are laid out for ld_r = 128 ceil(n_r / 128) rows, so up to ld_r - n_r new points fit without moving

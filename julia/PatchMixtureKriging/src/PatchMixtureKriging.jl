@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, querymixtureGP_cov_multi, appendmixtureGP!, capacitymixtureGP,
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, querymixtureGP_cov_multi, samplemixtureGP_blocks, appendmixtureGP!, capacitymixtureGP,
        removemixtureGP!, removablemixtureGP, reservemixtureGP!
 
 # ------------------------------------------------------------------------------------------ errors
@@ -1244,6 +1244,74 @@ function querymixtureGP_cov_multi(Xq::Vector{Vector{Float64}}, η::MixtureGPType
               "pmk_query_fetch_multi")
         check(ccall((:pmk_query_fetch_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], Cov, max(Nq, 1)), "pmk_query_fetch_cov")
         return Yq, Vq, Cov
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""samplemixtureGP_blocks(Xq, η, root, levels, radius, δ, weight_θ, Z; multi = false, region = 0) -> (E, jitter, total): the zero-mean
+part E (Nq x n) of n joint posterior draws of the blended field from the region blocks, without the Nq x Nq covariance
+(pmk_query_items_cov_blocks, pmk_query_factor_cov, pmk_query_draw): Nq may exceed 16384.  Z (ldz x n, ldz >= total) holds
+independent standard normals, column s for draw s, row p for the sorted item p; since total depends on the plan, a call
+with Z = zeros(0, 0) returns (zeros(Nq, 0), 0.0, total) and draws nothing.  The caller adds the blended mean; for R target
+columns (multi = true, after fitmixtureGPmulti!) one call per column with independent Z.  The jitter ladder runs per region:
+rel = 0, then for the failed regions 2^-52 and x 10 while rel <= 2^-26, on the scale trace S_r / m_r; jitter is the largest
+absolute value added.  Throws if a region that holds items belongs to a failed patch or cannot be factored.  region = r > 0
+also returns L_r, the lower-triangular factor of the block of region r (pmk_query_get_items_cov_factor)."""
+function samplemixtureGP_blocks(Xq::Vector{Vector{Float64}}, η::MixtureGPType{Float64}, root, levels, radius::Float64,
+                                δ::Float64, weight_θ, Z::Matrix{Float64}; multi::Bool = false, region::Int = 0)
+    η.model == C_NULL && throw(PMKError("fitmixtureGP! must run before samplemixtureGP_blocks"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    P = Int(ccall((:pmk_model_num_patches, libpmk), Int64, (Ptr{Cvoid},), η.model))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        total = Ref{Int64}(0)
+        check(ccall((:pmk_query_counts, libpmk), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}), q[], total,
+                    Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL)), "pmk_query_counts")
+        size(Z, 2) == 0 && return zeros(Nq, 0), 0.0, Int(total[])
+        size(Z, 1) >= total[] || throw(PMKError("Z has $(size(Z, 1)) rows, the plan $(total[]) items"))
+        if multi
+            check(ccall((:pmk_query_items_multi_fitted, libpmk), Cint, (Ptr{Cvoid}, Cint), q[], 1), "pmk_query_items_multi_fitted")
+        else
+            check(ccall((:pmk_query_items_fitted, libpmk), Cint, (Ptr{Cvoid},), q[]), "pmk_query_items_fitted")
+        end
+        check(ccall((:pmk_query_items_cov_blocks, libpmk), Cint, (Ptr{Cvoid}, Ptr{KernelDesc}, Cint), q[], Ptr{KernelDesc}(C_NULL),
+                    multi ? 1 : 0), "pmk_query_items_cov_blocks")
+        roff = Vector{Int64}(undef, P + 1)
+        check(ccall((:pmk_query_region_offsets, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int64}), q[], roff), "pmk_query_region_offsets")
+        rel = zeros(P); finfo = Vector{Int32}(undef, P); jit = Vector{Float64}(undef, P)
+        while true
+            check(ccall((:pmk_query_factor_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}), q[], rel), "pmk_query_factor_cov")
+            check(ccall((:pmk_query_factor_info, libpmk), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}), q[], finfo, jit),
+                  "pmk_query_factor_info")
+            for r = 1:P
+                finfo[r] == -1 && roff[r + 1] > roff[r] &&
+                    throw(PMKError("samplemixtureGP_blocks: region $r holds items of the batch and its patch is failed"))
+            end
+            failed = findall(>(0), finfo)
+            isempty(failed) && break
+            for r in failed
+                rel[r] = rel[r] == 0.0 ? 2.0^-52 : 10.0 * rel[r]
+                rel[r] <= 2.0^-26 || throw(PMKError("samplemixtureGP_blocks: the block of region $r is not positive definite " *
+                                                    "with a jitter of up to 2^-26 trace / m"))
+            end
+        end
+        n = size(Z, 2)
+        E = Matrix{Float64}(undef, Nq, n)
+        check(ccall((:pmk_query_draw, libpmk), Cint, (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+                    q[], Ref(desc(weight_θ)), n, Z, size(Z, 1), E, max(Nq, 1)), "pmk_query_draw")
+        jitter = P > 0 ? maximum(jit) : 0.0
+        region == 0 && return E, jitter, Int(total[])
+        m = Ref{Int64}(0)
+        check(ccall((:pmk_query_get_items_cov_factor, libpmk), Cint, (Ptr{Cvoid}, Int64, Ref{Int64}, Ptr{Float64}, Int64),
+                    q[], region - 1, m, Ptr{Float64}(C_NULL), 0), "pmk_query_get_items_cov_factor")
+        L = Matrix{Float64}(undef, m[], m[])
+        check(ccall((:pmk_query_get_items_cov_factor, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Int64),
+                    q[], region - 1, Ptr{Int64}(C_NULL), L, max(m[], 1)), "pmk_query_get_items_cov_factor")
+        return E, jitter, Int(total[]), L
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end

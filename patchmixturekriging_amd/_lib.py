@@ -191,6 +191,11 @@ SIGNATURES = {
     "pmk_predict_mixture_cov_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, _dp, _dp,
                                                  C.c_int64]),
     "pmk_query_items_cov_multi": (C.c_int, [_vp, _kp]),
+    "pmk_query_items_cov_blocks": (C.c_int, [_vp, _kp, C.c_int]),
+    "pmk_query_factor_cov": (C.c_int, [_vp, _dp]),
+    "pmk_query_factor_info": (C.c_int, [_vp, _i32p, _dp]),
+    "pmk_query_get_items_cov_factor": (C.c_int, [_vp, C.c_int64, _ip, _dp, C.c_int64]),
+    "pmk_query_draw": (C.c_int, [_vp, _kp, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "pmk_predict_mixture_cov_multi_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64,
                                                        _dp, _dp, C.c_int64]),
     "pmk_model_capacity": (C.c_int, [_vp, _ip]),

@@ -498,17 +498,6 @@ int pmk_model_create_ex(pmk_ctx *ctx, int D, int64_t P, const int64_t *n, const 
 }
 
 // ------------------------------------------------------------------------------------------ tree + global points
-// true if p is device memory (what the gather kernels can read); a plain or pinned host array is staged first
-static bool is_device_pointer(const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();                 // an unregistered host pointer: not an error of ours
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
 // a global array of `count` doubles where the gather kernels can read it: the caller's device pointer as it is (nothing
 // waits), or a copy in the model's staging buffer (returns once the host array has been read)
 static int global_source(pmk_model *m, const double *src, size_t count, const double **d_src)

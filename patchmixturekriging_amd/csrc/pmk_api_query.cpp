@@ -283,6 +283,9 @@ void pmk_query_destroy(pmk_query *q)
     dev_free(q->d_gv); dev_free(q->d_gh); dev_free(q->d_dvq); dev_free(q->d_vgpre);
     dev_free(q->d_cov_v); dev_free(q->d_cov_s); dev_free(q->d_cov); dev_free(q->d_cov_tasks); dev_free(q->d_cov_pairs);
     dev_free(q->d_cov_goff); dev_free(q->d_cov_z); dev_free(q->d_cov_flags);
+    dev_free(q->d_cov_f); dev_free(q->d_fdesc); dev_free(q->d_forder); dev_free(q->d_ftasks); dev_free(q->d_finfo);
+    dev_free(q->d_fact); dev_free(q->d_fjit); dev_free(q->d_frel); dev_free(q->d_draw_t); dev_free(q->d_draw_z);
+    dev_free(q->d_draw_e);
     dev_free(q->d_loo_x);              // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
@@ -1065,8 +1068,8 @@ static int fetch_cov_common(pmk_query *q, double *Cov, int64_t ldc, hipMemcpyKin
 
 // The region blocks of the current plan.  multi: the multi-output path (pmk_query_items_cov_multi), whose blocks carry the
 // term z_a . z_b of the model's trend; its checks come before any launch, and with no trend in force it runs what the
-// single-output call runs.
-static int items_cov_common(pmk_query *q, const pmk_kernel_desc *th, bool multi, const char *who)
+// single-output call runs.  limit: refuse a batch above PMK_COV_MAX_QUERIES (the calls whose blocks feed the Nq x Nq result).
+static int items_cov_common(pmk_query *q, const pmk_kernel_desc *th, bool multi, bool limit, const char *who)
 {
     if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
     pmk_model *m = q->m;
@@ -1097,11 +1100,12 @@ static int items_cov_common(pmk_query *q, const pmk_kernel_desc *th, bool multi,
             if (int rc = cov_kernel_ok(&m->ths[r], m->D, who, "the model's own theta")) return rc;
         th = fitted_theta(m);
     }
-    if (int rc = cov_batch_ok(q->Nq, who)) return rc;
+    if (limit)
+        if (int rc = cov_batch_ok(q->Nq, who)) return rc;
     pmk_ctx *c = m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    q->cov_items = q->mixed_cov = false;
+    q->cov_items = q->mixed_cov = q->cov_factored = false;
     q->cov_trend_q = 0;
     std::vector<CovTask> tasks;
     std::vector<CovPair> pairs;
@@ -1142,12 +1146,12 @@ extern "C" {
 
 int pmk_query_items_cov(pmk_query *q, const pmk_kernel_desc *th)
 {
-    return items_cov_common(q, th, false, "pmk_query_items_cov");
+    return items_cov_common(q, th, false, true, "pmk_query_items_cov");
 }
 
 int pmk_query_items_cov_multi(pmk_query *q, const pmk_kernel_desc *th)
 {
-    return items_cov_common(q, th, true, "pmk_query_items_cov_multi");
+    return items_cov_common(q, th, true, true, "pmk_query_items_cov_multi");
 }
 
 int pmk_query_mix_cov(pmk_query *q, const pmk_kernel_desc *weight_th)
@@ -1160,6 +1164,7 @@ int pmk_query_mix_cov(pmk_query *q, const pmk_kernel_desc *weight_th)
     }
     if (!q->cov_items) { set_error("%s: pmk_query_items_cov has not run on this plan", who); return -2; }
     if (int rc = blend_profile_ok(weight_th, who)) return rc;
+    if (int rc = cov_batch_ok(q->Nq, who)) return rc;       // blocks of pmk_query_items_cov_blocks on a larger batch
     pmk_ctx *c = q->m->ctx;
     PMK_HIP(hipSetDevice(c->device));
     q->mixed_cov = false;
@@ -1260,6 +1265,208 @@ int pmk_predict_mixture_cov_multi_fitted(pmk_model *m, const pmk_kernel_desc *we
             int rc = (Yq || Vq) ? pmk_query_fetch_multi(q, Yq, ldyq, Vq) : 0;
             return !rc && Cov ? pmk_query_fetch_cov(q, Cov, ldc) : rc;
         });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ draws from the region blocks
+// The factors' geometry from the plan's region offsets: the padded offsets, the regions by descending tile count (step k
+// of the factorisation takes the first fstep_regions[k] of them) and every tile row of every region.
+static int factor_layout(pmk_query *q, hipStream_t s, const char *who)
+{
+    const pmk_model *m = q->m;
+    const int64_t P = m->P;
+    std::vector<DrawRegion> desc((size_t)P);
+    std::vector<int32_t> order((size_t)P);
+    std::vector<DrawTask> tasks;
+    q->cov_foff.assign((size_t)P + 1, 0);
+    int32_t max_nt = 0;
+    for (int64_t r = 0; r < P; ++r) {
+        const int64_t b = q->roff[(size_t)(m->leaf_base + r)], mr = q->roff[(size_t)(m->leaf_base + r + 1)] - b;
+        DrawRegion &d = desc[(size_t)r];
+        d.soff = q->cov_goff[(size_t)r];
+        d.foff = q->cov_foff[(size_t)r];
+        d.p0 = b;
+        d.m = (int32_t)mr;
+        d.nt = (int32_t)((mr + DRAW_TILE - 1) / DRAW_TILE);
+        const int64_t ld = (int64_t)DRAW_TILE * d.nt;
+        q->cov_foff[(size_t)r + 1] = d.foff + ld * ld;
+        max_nt = std::max(max_nt, d.nt);
+        order[(size_t)r] = (int32_t)r;
+        for (int32_t i = 0; i < d.nt; ++i) tasks.push_back({(int32_t)r, i});
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return desc[(size_t)a].nt > desc[(size_t)b].nt; });
+    q->fstep_regions.assign((size_t)max_nt, 0);
+    for (int64_t r = 0; r < P; ++r)
+        for (int32_t k = 0; k < desc[(size_t)r].nt; ++k) ++q->fstep_regions[(size_t)k];
+    q->nftasks = (int64_t)tasks.size();
+    if (int rc = grow_sized(q->d_cov_f, q->cov_f_cap, q->cov_foff[(size_t)P], s, who, "the padded factors")) return rc;
+    if (int rc = grow_sized(q->d_fdesc, q->fdesc_cap, P, s, who, "the region descriptors")) return rc;
+    if (int rc = grow_sized(q->d_forder, q->forder_cap, P, s, who, "the region order")) return rc;
+    if (int rc = grow_sized(q->d_ftasks, q->ftasks_cap, q->nftasks, s, who, "the tile rows")) return rc;
+    if (int rc = grow_sized(q->d_finfo, q->finfo_cap, P, s, who, "the status words")) return rc;
+    if (int rc = grow_sized(q->d_fact, q->fact_cap, P, s, who, "the region marks")) return rc;
+    if (int rc = grow_sized(q->d_fjit, q->fjit_cap, P, s, who, "the jitter values")) return rc;
+    if (int rc = grow_sized(q->d_frel, q->frel_cap, 2 * P, s, who, "the relative jitters")) return rc;
+    if (P > 0) {
+        PMK_HIP(hipMemcpyAsync(q->d_fdesc, desc.data(), sizeof(DrawRegion) * (size_t)P, hipMemcpyHostToDevice, s));
+        PMK_HIP(hipMemcpyAsync(q->d_forder, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, s));
+    }
+    if (!tasks.empty())
+        PMK_HIP(hipMemcpyAsync(q->d_ftasks, tasks.data(), sizeof(DrawTask) * tasks.size(), hipMemcpyHostToDevice, s));
+    PMK_HIP(hipStreamSynchronize(s));       // the sources are locals
+    return 0;
+}
+
+// draws of a chunk: the workspace holds total x chunk doubles, at most 256 MiB, at least one tile of draws
+static int64_t draw_chunk(int64_t total, int64_t n_draws)
+{
+    const int64_t fit = ((int64_t)1 << 25) / std::max<int64_t>(total, 1) / DRAW_TILE * DRAW_TILE;
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(fit, DRAW_TILE), 256);
+    return std::min(chunk, (n_draws + DRAW_TILE - 1) / DRAW_TILE * DRAW_TILE);
+}
+
+extern "C" {
+
+int pmk_query_items_cov_blocks(pmk_query *q, const pmk_kernel_desc *th, int multi)
+{
+    return items_cov_common(q, th, multi != 0, false, "pmk_query_items_cov_blocks");
+}
+
+int pmk_query_factor_cov(pmk_query *q, const double *rel)
+{
+    static const char who[] = "pmk_query_factor_cov";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (!q->cov_items) { set_error("%s: no region blocks on this plan (pmk_query_items_cov, _multi or _blocks)", who); return -2; }
+    const pmk_model *m = q->m;
+    const int64_t P = m->P;
+    std::vector<double> relv((size_t)P, 0.0);
+    if (rel)
+        for (int64_t r = 0; r < P; ++r) {
+            if (!(rel[r] >= 0.0) || !(rel[r] <= 1.79769313486231570815e308)) {
+                set_error("%s: rel[%lld] = %g is negative or not finite", who, (long long)r, rel[r]);
+                return -2;
+            }
+            relv[(size_t)r] = rel[r];
+        }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const bool have = q->cov_factored;
+    q->cov_factored = false;
+    if (!have)
+        if (int rc = factor_layout(q, s, who)) return rc;
+    if (P > 0) {
+        PMK_HIP(hipMemcpyAsync(q->d_frel + P, relv.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, s));
+        PMK_HIP(hipStreamSynchronize(s));   // `relv` is a local
+    }
+    c->tic("factor_cov");
+    const int rc = launch_factor_cov(q, have ? 1 : 0, s);
+    c->toc("factor_cov");
+    if (rc) return rc;
+    q->cov_factored = true;
+    return 0;
+}
+
+int pmk_query_factor_info(pmk_query *q, int32_t *finfo, double *jitter)
+{
+    static const char who[] = "pmk_query_factor_info";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (!q->cov_items || !q->cov_factored) { set_error("%s: pmk_query_factor_cov has not run on these blocks", who); return -2; }
+    const pmk_model *m = q->m;
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    std::vector<int32_t> fi((size_t)m->P);
+    if (m->P > 0) PMK_HIP(hipMemcpy(fi.data(), q->d_finfo, sizeof(int32_t) * (size_t)m->P, hipMemcpyDeviceToHost));
+    if (jitter && m->P > 0) PMK_HIP(hipMemcpy(jitter, q->d_fjit, sizeof(double) * (size_t)m->P, hipMemcpyDeviceToHost));
+    int any = 0;
+    for (int64_t r = 0; r < m->P; ++r) {
+        if (finfo) finfo[r] = fi[(size_t)r];
+        any |= fi[(size_t)r] != 0;
+    }
+    return any;
+}
+
+int pmk_query_get_items_cov_factor(pmk_query *q, int64_t region, int64_t *m_out, double *L, int64_t ldl)
+{
+    static const char who[] = "pmk_query_get_items_cov_factor";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (!q->cov_items) { set_error("%s: pmk_query_items_cov has not run on this plan", who); return -2; }
+    if (!q->cov_factored) { set_error("%s: pmk_query_factor_cov has not run on these blocks", who); return -2; }
+    const pmk_model *m = q->m;
+    if (region < m->leaf_base || region >= m->leaf_base + m->P) {
+        set_error("%s: region %lld is outside this model's leaves [%lld, %lld)", who, (long long)region,
+                  (long long)m->leaf_base, (long long)(m->leaf_base + m->P));
+        return -3;
+    }
+    const int64_t mr = q->roff[(size_t)region + 1] - q->roff[(size_t)region];
+    if (m_out) *m_out = mr;
+    if (L && ldl < mr) { set_error("%s: ldl = %lld < m = %lld", who, (long long)ldl, (long long)mr); return -4; }
+    pmk_ctx *c = m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    PMK_HIP(hipStreamSynchronize(c->stream));
+    if (mr == 0 || !L) return 0;
+    const int64_t ld = (mr + DRAW_TILE - 1) / DRAW_TILE * DRAW_TILE;
+    PMK_HIP(hipMemcpy2D(L, sizeof(double) * (size_t)ldl, q->d_cov_f + q->cov_foff[(size_t)(region - m->leaf_base)],
+                        sizeof(double) * (size_t)ld, sizeof(double) * (size_t)mr, (size_t)mr, hipMemcpyDeviceToHost));
+    // the tiles above the diagonal are never written on the device
+    for (int64_t b = 1; b < mr; ++b)
+        for (int64_t a = 0; a < b; ++a) L[a + ldl * b] = 0.0;
+    return 0;
+}
+
+int pmk_query_draw(pmk_query *q, const pmk_kernel_desc *weight_th, int64_t n_draws, const double *z, int64_t ldz, double *E,
+                   int64_t lde)
+{
+    static const char who[] = "pmk_query_draw";
+    if (!q || !q->planned) { set_error("%s: query is not planned", who); return -1; }
+    if (q->explicit_items) {
+        set_error("%s: the query was made by pmk_query_create_items: its items belong to no blend", who);
+        return -2;
+    }
+    if (!q->cov_items || !q->cov_factored) { set_error("%s: pmk_query_factor_cov has not run on these blocks", who); return -2; }
+    if (int rc = blend_profile_ok(weight_th, who)) return rc;
+    if (n_draws < 0) { set_error("%s: n_draws = %lld", who, (long long)n_draws); return -2; }
+    if (n_draws == 0) return 0;
+    if (!z || !E) { set_error("%s: %s is NULL", who, z ? "E" : "z"); return -2; }
+    if (ldz < q->total || lde < q->Nq) {
+        set_error("%s: ldz = %lld, lde = %lld: at least total_items = %lld and Nq = %lld", who, (long long)ldz, (long long)lde,
+                  (long long)q->total, (long long)q->Nq);
+        return -4;
+    }
+    if (q->Nq == 0) return 0;
+    pmk_ctx *c = q->m->ctx;
+    PMK_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const bool z_dev = is_device_pointer(z), e_dev = is_device_pointer(E);
+    const int64_t chunk = draw_chunk(q->total, n_draws);
+    if (int rc = grow_sized(q->d_draw_t, q->draw_t_cap, q->total * chunk, s, who, "the workspace of L Z")) return rc;
+    if (!z_dev)
+        if (int rc = grow_sized(q->d_draw_z, q->draw_z_cap, q->total * chunk, s, who, "the device copy of z")) return rc;
+    if (!e_dev)
+        if (int rc = grow_sized(q->d_draw_e, q->draw_e_cap, q->Nq * chunk, s, who, "the device copy of E")) return rc;
+    c->tic("draw");
+    int rc = 0;
+    for (int64_t s0 = 0; s0 < n_draws && !rc; s0 += chunk) {
+        const int64_t n = std::min(chunk, n_draws - s0);
+        const double *dz = z + ldz * s0;
+        int64_t dldz = ldz;
+        if (!z_dev) {
+            PMK_HIP(hipMemcpy2DAsync(q->d_draw_z, sizeof(double) * (size_t)q->total, dz, sizeof(double) * (size_t)ldz,
+                                     sizeof(double) * (size_t)q->total, (size_t)n, hipMemcpyHostToDevice, s));
+            dz = q->d_draw_z;
+            dldz = q->total;
+        }
+        rc = launch_draw(q, *weight_th, dz, dldz, n, e_dev ? E + lde * s0 : q->d_draw_e, e_dev ? lde : q->Nq, s);
+        if (!rc && !e_dev)
+            PMK_HIP(hipMemcpy2DAsync(E + lde * s0, sizeof(double) * (size_t)lde, q->d_draw_e, sizeof(double) * (size_t)q->Nq,
+                                     sizeof(double) * (size_t)q->Nq, (size_t)n, hipMemcpyDeviceToHost, s));
+        // a host chunk is read or written by the copies above: the next one reuses the staging buffers
+        if (!rc && (!z_dev || !e_dev)) PMK_HIP(hipStreamSynchronize(s));
+    }
+    c->toc("draw");
+    return rc;
 }
 
 }  // extern "C"

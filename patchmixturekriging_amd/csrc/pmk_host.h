@@ -99,6 +99,17 @@ public:
     }
 };
 
+// true if p is device memory (what a kernel can read or write); a plain or pinned host array is staged
+inline bool is_device_pointer(const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                 // an unregistered host pointer: not an error of ours
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
 // the theta the launchers take for the model's own hyperparameters: one descriptor after a plain fit, else null for the
 // per-patch device arrays
 inline const pmk_kernel_desc *fitted_theta(const pmk_model *m) { return m->hyper_uniform ? &m->th : nullptr; }
@@ -139,7 +150,7 @@ inline void reset_item_state(pmk_query *q)
     q->vgrad_items = q->mixed_vgrad = false;
     // blocks with a trend's term (pmk_query_items_cov_multi) were computed from the item rows that now go
     if (q->cov_trend_q > 0) {
-        q->cov_items = q->mixed_cov = false;
+        q->cov_items = q->mixed_cov = q->cov_factored = false;
         q->cov_trend_q = 0;
     }
 }
@@ -147,7 +158,7 @@ inline void reset_item_state(pmk_query *q)
 inline void reset_plan_state(pmk_query *q)
 {
     reset_item_state(q);
-    q->cov_items = q->mixed_cov = false;
+    q->cov_items = q->mixed_cov = q->cov_factored = false;
     q->cov_trend_q = 0;
 }
 

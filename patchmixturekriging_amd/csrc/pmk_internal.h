@@ -99,6 +99,18 @@ struct CovTask {
 };
 struct CovPair { int32_t ta, tb; };   // two strips of one region, ta <= tb
 
+// A region block and its Cholesky factor (pmk_draw.hip).  The factor is padded to nt tiles of DRAW_TILE rows, column-major
+// with leading dimension DRAW_TILE nt, the identity in the padding.  Built on the host from the plan's region offsets.
+constexpr int DRAW_TILE = 32;
+struct DrawRegion {
+    int64_t soff;     // element offset of the m x m block S_r in the block buffer (cov_goff)
+    int64_t foff;     // element offset of the padded factor in the factor buffer
+    int64_t p0;       // first sorted item of the region
+    int32_t m;        // items of the region
+    int32_t nt;       // tiles: ceil(m / DRAW_TILE)
+};
+struct DrawTask { int32_t region, tile; };   // a tile row of a region's factor
+
 // A patch that loses rows (pmk_remove.hip): its rows are rows[first .. first + count), ascending.
 struct RemoveTask {
     int32_t region;   // local patch
@@ -312,6 +324,22 @@ struct pmk_query {
     int cov_trend_q = 0;
     double *d_cov_z = nullptr; int64_t cov_z_cap = 0;             // sorted items x TQ_MAX: z = L_G^-1 rho
     int32_t *d_cov_flags = nullptr; int64_t cov_flags_cap = 0;    // P: info != 0 or tinfo != 0
+    // posterior draws from the region blocks (pmk_draw.hip).  cov_factored: pmk_query_factor_cov has run on the current
+    // blocks; whatever discards the blocks, and new blocks, discard the factors.  All buffers grow only.
+    bool cov_factored = false;
+    double *d_cov_f = nullptr; int64_t cov_f_cap = 0;             // padded factors, at cov_foff[r]
+    std::vector<int64_t> cov_foff;      // host copy: prefix of (DRAW_TILE nt_r)^2
+    pmk::DrawRegion *d_fdesc = nullptr; int64_t fdesc_cap = 0;    // P
+    int32_t *d_forder = nullptr; int64_t forder_cap = 0;          // P: the regions by descending tile count
+    std::vector<int32_t> fstep_regions; // regions with more than k tiles, per block step k
+    pmk::DrawTask *d_ftasks = nullptr; int64_t ftasks_cap = 0, nftasks = 0;     // every tile row of every region
+    int32_t *d_finfo = nullptr; int64_t finfo_cap = 0;            // P status words (pmk_query_factor_info)
+    int32_t *d_fact = nullptr; int64_t fact_cap = 0;              // P: the region is factored by the current call
+    double *d_fjit = nullptr; int64_t fjit_cap = 0;               // P: the absolute jitter that was added
+    double *d_frel = nullptr; int64_t frel_cap = 0;               // 2 P: rel of the factors held, rel of the current call
+    double *d_draw_t = nullptr; int64_t draw_t_cap = 0;           // total x (draw chunk): T_r = L_r Z_r in sorted-item order
+    double *d_draw_z = nullptr; int64_t draw_z_cap = 0;           // device copy of a chunk of host z
+    double *d_draw_e = nullptr; int64_t draw_e_cap = 0;           // a chunk of E for a host pointer
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -397,6 +425,9 @@ int launch_trend_vgrad(pmk_query *q, hipStream_t s);
 int launch_mix_vgrad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_cov(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s);
 int launch_cov_trend(pmk_query *q, hipStream_t s);
+int launch_factor_cov(pmk_query *q, int have_factors, hipStream_t s);
+int launch_draw(pmk_query *q, const pmk_kernel_desc &wth, const double *d_z, int64_t ldz, int64_t n, double *d_E,
+                int64_t lde, hipStream_t s);
 int launch_loo_scatter_multi(pmk_query *q, const pmk_query *in, int noisy, int want_var, const int32_t *d_mark,
                              const int64_t *d_off, hipStream_t s);
 int launch_export_requests(pmk_query *q, int64_t first, int64_t n, double *x_out, int32_t *region_out, hipStream_t s);

@@ -64,6 +64,11 @@ int launch_trend_vgrad(pmk_query *, hipStream_t) { return no_gpu("launch_trend_v
 int launch_mix_vgrad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_vgrad"); }
 int launch_mix_cov(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_mix_cov"); }
 int launch_cov_trend(pmk_query *, hipStream_t) { return no_gpu("launch_cov_trend"); }
+int launch_factor_cov(pmk_query *, int, hipStream_t) { return no_gpu("launch_factor_cov"); }
+int launch_draw(pmk_query *, const pmk_kernel_desc &, const double *, int64_t, int64_t, double *, int64_t, hipStream_t)
+{
+    return no_gpu("launch_draw");
+}
 int launch_loo_scatter_multi(pmk_query *, const pmk_query *, int, int, const int32_t *, const int64_t *, hipStream_t)
 {
     return no_gpu("launch_loo_scatter_multi");

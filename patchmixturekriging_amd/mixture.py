@@ -1018,6 +1018,80 @@ class DeviceQuery:
                    "pmk_query_get_items_cov")
         return idx[:m.value], S[:m.value, :m.value]
 
+    # ---- posterior draws from the region blocks (pmk_draw.hip)
+    def items_cov_blocks(self, theta=None, multi=False):
+        """pmk_query_items_cov_blocks: the region blocks of items_cov (multi=False) or items_cov_multi (multi=True) for a
+        batch of any size: what factor_cov and draw need.  mix_cov refuses such blocks on more than 16384 queries."""
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            _refuse_closure_kernel(theta, "items_cov_blocks")
+            d = theta.desc()
+            ptr = C.byref(d)
+        _lib.check(self.L.pmk_query_items_cov_blocks(self.h, ptr, 1 if multi else 0), "pmk_query_items_cov_blocks")
+
+    def factor_cov(self, rel=None):
+        """pmk_query_factor_cov: the Cholesky factor of every region block, block r as S_r + rel[r] (trace S_r / m_r) I
+        (rel: P values, None for zeros).  Enqueues; a region already factored with the same rel[r] keeps its factor."""
+        if rel is None:
+            ptr = None
+        else:
+            rel = np.ascontiguousarray(rel, dtype=np.float64)
+            if rel.shape != (int(self.model.P),):
+                raise ValueError("rel must hold one value per patch (%d), not %s" % (self.model.P, rel.shape))
+            ptr = _d(rel)
+        _lib.check(self.L.pmk_query_factor_cov(self.h, ptr), "pmk_query_factor_cov")
+
+    def factor_info(self):
+        """pmk_query_factor_info -> (finfo [P] int32, jitter [P]): 0 factored or empty, k > 0 pivot k is <= 0 or NaN, -1 the
+        patch is failed or its trend flagged; the absolute jitter that was added.  Blocks."""
+        P = int(self.model.P)
+        finfo, jitter = np.zeros(P, dtype=np.int32), np.zeros(P)
+        rc = self.L.pmk_query_factor_info(self.h, finfo.ctypes.data_as(C.POINTER(C.c_int32)), _d(jitter))
+        if rc < 0:
+            _lib.check(rc, "pmk_query_factor_info")
+        return finfo, jitter
+
+    def item_cov_factor(self, region):
+        """pmk_query_get_items_cov_factor -> L [m, m], lower triangular, of one global region; rows as in item_covs"""
+        m = C.c_int64()
+        _lib.check(self.L.pmk_query_get_items_cov_factor(self.h, int(region), C.byref(m), None, 0),
+                   "pmk_query_get_items_cov_factor")
+        n = max(m.value, 1)
+        buf = np.zeros((n, n))                      # buf[b, a] = L[a + ldl b]
+        _lib.check(self.L.pmk_query_get_items_cov_factor(self.h, int(region), None, _d(buf), n),
+                   "pmk_query_get_items_cov_factor")
+        return np.ascontiguousarray(buf[:m.value, :m.value].T)
+
+    def draw(self, weight_theta, z, out=None):
+        """pmk_query_draw: z [n_draws, total_items], row s the standard normals of draw s in sorted-item order (region r
+        owns the columns region_offsets[r] .. region_offsets[r + 1] - 1, in the row order of item_covs) -> E [n_draws, Nq],
+        the zero-mean part of the draws.  z and out are numpy arrays (the call blocks) or device arrays such as torch
+        tensors (the call enqueues on the context's stream); out defaults to an array of the kind of z."""
+        _refuse_closure_kernel(weight_theta, "draw")
+        za = GlobalArray(z, "z")
+        if len(za.shape) != 2 or za.shape[1] != int(self.total):
+            raise ValueError("z must have shape (n_draws, %d), not %s" % (self.total, za.shape))
+        n = za.shape[0]
+        if za.shape[1] > 1 and za.strides[1] != 1:
+            raise ValueError("z must have contiguous rows")
+        ldz = za.strides[0] if n > 1 else max(int(self.total), 1)
+        if out is None:
+            if za.device:
+                import torch
+                out = torch.empty((n, self.Nq), dtype=torch.float64, device=z.device)
+            else:
+                out = np.empty((n, self.Nq))
+        ea = GlobalArray(out, "out")
+        if ea.shape != (n, self.Nq) or (self.Nq > 1 and ea.strides[1] != 1):
+            raise ValueError("out must have shape (%d, %d) and contiguous rows, not %s" % (n, self.Nq, ea.shape))
+        lde = ea.strides[0] if n > 1 else max(self.Nq, 1)
+        d = weight_theta.desc()
+        _lib.check(self.L.pmk_query_draw(self.h, C.byref(d), n, za.ptr, ldz, ea.ptr, lde), "pmk_query_draw")
+        return out
+
     def debug(self):
         home = np.empty(self.Nq, dtype=np.int64)
         off = np.empty(self.Nq + 1, dtype=np.int64)
@@ -1685,15 +1759,82 @@ def querymixtureGP_cov(Xq, eta, root, levels, radius, delta, weight_theta):
     return Yq, Vq, q.fetch_cov()
 
 
-def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None):
+def _sample_blocks(q, multi, weight_theta, n_draws, generator, z, who):
+    """method="blocks" of the sampling front ends, on a planned query whose means are mixed: the region blocks, their
+    factors under the per-region jitter ladder, and the zero-mean draws E [n_draws, Nq] or [n_draws, Nq, R]
+    -> (E, jitter)"""
+    import torch
+
+    dev = torch.device("cuda", q.model.ctx.device)
+    P, R = int(q.model.P), (int(q.model.R) if multi else None)
+    q.items_cov_blocks(None, multi)
+    held = np.diff(q.region_offsets(P)) > 0
+    rel = np.zeros(P)
+    q.factor_cov(rel)
+    while True:
+        finfo, jit = q.factor_info()
+        bad = np.nonzero(held & (finfo == -1))[0]
+        if len(bad):
+            raise np.linalg.LinAlgError("%s: region %d holds items of the batch and its patch is failed (DeviceModel.info())"
+                                        " or its trend is flagged (DeviceModel.trend_info())" % (who, int(bad[0])))
+        failed = np.nonzero(finfo > 0)[0]
+        if not len(failed):
+            break
+        nxt = np.where(rel[failed] == 0.0, 2.0 ** -52, 10.0 * rel[failed])
+        over = failed[~(nxt <= 2.0 ** -26)]
+        if len(over):
+            raise np.linalg.LinAlgError("%s: the block of region %d is not positive definite with a jitter of up to 2^-26 "
+                                        "trace / m" % (who, int(over[0])))
+        rel[failed] = nxt
+        q.factor_cov(rel)
+    jitter = float(jit.max()) if P else 0.0
+    n, total = int(n_draws), int(q.total)
+    shape = (n, total) if R is None else (n, total, R)
+    if z is None:
+        z = torch.randn(shape, dtype=torch.float64, device=dev, generator=generator)
+    else:
+        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
+        if tuple(z.shape) != shape:
+            raise ValueError("z must have shape %s, not %s" % (shape, tuple(z.shape)))
+    torch.cuda.synchronize(dev)                 # torch wrote z on its own stream, the library reads on the context's
+    if R is None:
+        E = q.draw(weight_theta, z.contiguous())
+    else:
+        E = torch.stack([q.draw(weight_theta, z[:, :, c].contiguous()) for c in range(R)], dim=2)
+    q.model.ctx.synchronize()
+    return E, jitter
+
+
+def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None, method="dense"):
     """posterior draws of the latent blended field at Xq -> (draws [n_draws, Nq] as a torch device tensor, jitter).
     The joint covariance of querymixtureGP_cov is fetched into a device tensor and factored with
     torch.linalg.cholesky_ex; if that fails, jitter * I is added, starting at 2^-52 trace / Nq and multiplied by 10 up to
     2^-26 trace / Nq, after which LinAlgError is raised.  A batch that blends a patch whose factorisation failed has NaN
     in its covariance and raises LinAlgError before any factorisation.  The jitter that was used is returned (0.0: none).  z
-    [n_draws, Nq]: the standard normals to use; otherwise they are drawn from `generator`.  draws = Yq + z L^T."""
+    [n_draws, Nq]: the standard normals to use; otherwise they are drawn from `generator`.  draws = Yq + z L^T.
+
+    method="blocks" never forms the Nq x Nq matrix: every region block is factored on its own (DeviceQuery.factor_cov)
+    and the draws are the blend of L_r z_r (DeviceQuery.draw), so Nq may exceed 16384.  z is then [n_draws, total_items]
+    in sorted-item order.  The jitter ladder runs per region, for the failed regions only: rel = 2^-52, then x 10 while
+    rel <= 2^-26, on the scale trace S_r / m_r; after that LinAlgError names the region.  A region that holds items and
+    whose patch is failed raises LinAlgError before any draw.  The jitter returned is the largest absolute value added."""
     import torch
 
+    if method not in ("dense", "blocks"):
+        raise ValueError("method must be \"dense\" or \"blocks\", not %r" % (method,))
+    if method == "blocks":
+        who = "samplemixtureGP"
+        _refuse_closure_kernel(weight_theta, who)
+        theta = getattr(getattr(eta, "_model", None), "theta", None)
+        if theta is not None:
+            _refuse_closure_kernel(theta, who)
+        q = _patches_query(Xq, eta, root, radius, delta, who)
+        q.items_fitted()
+        q.mix(weight_theta)
+        Yq = torch.empty(q.Nq, dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))
+        q.fetch_into(Yq)
+        E, jitter = _sample_blocks(q, False, weight_theta, n_draws, generator, z, who)
+        return Yq[None, :] + E, jitter
     q = _cov_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP")
     dev = torch.device("cuda", q.model.ctx.device)
     Nq = q.Nq
@@ -1753,15 +1894,35 @@ def querymixtureGP_cov_multi(Xq, eta, root, levels, radius, delta, weight_theta)
     return Yq, Vq, q.fetch_cov()
 
 
-def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None):
+def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None,
+                          method="dense"):
     """posterior draws of the R latent blended fields at Xq -> (draws [n_draws, Nq, R] as a torch device tensor, jitter).
     The joint covariance of querymixtureGP_cov_multi is factored once (torch.linalg.cholesky_ex, the jitter ladder of
     samplemixtureGP) and serves every column: draws[:, :, c] = Yq[:, c] + z[:, :, c] L^T with independent standard normals
     per column.  z [n_draws, Nq, R]: the normals to use; otherwise they are drawn from `generator`.  A covariance that
     holds NaN (a batch that blends a patch whose factorisation failed or whose trend is flagged) raises LinAlgError
-    before any factorisation."""
+    before any factorisation.
+
+    method="blocks": as in samplemixtureGP, on the blocks of items_cov_multi; z is [n_draws, total_items, R] in sorted-item
+    order, and the factors serve every column."""
     import torch
 
+    if method not in ("dense", "blocks"):
+        raise ValueError("method must be \"dense\" or \"blocks\", not %r" % (method,))
+    if method == "blocks":
+        who = "samplemixtureGP_multi"
+        _refuse_closure_kernel(weight_theta, who)
+        theta = getattr(getattr(eta, "_model", None), "theta", None)
+        if theta is not None:
+            _refuse_closure_kernel(theta, who)
+        q = _patches_query(Xq, eta, root, radius, delta, who)
+        q.model._need(multi=True)
+        q.items_multi_fitted(True)
+        q.mix_multi(weight_theta)
+        Yq = torch.empty((int(q.model.R), q.Nq), dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))
+        q.fetch_multi_into(Yq.T)
+        E, jitter = _sample_blocks(q, True, weight_theta, n_draws, generator, z, who)
+        return Yq.T[None, :, :] + E, jitter
     q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP_multi")
     dev = torch.device("cuda", q.model.ctx.device)
     Nq, R = q.Nq, int(q.model.R)
