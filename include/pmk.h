@@ -34,6 +34,7 @@ extern "C" {
 
 #define PMK_VERSION 103
 #define PMK_MAX_OUTPUTS 16   /* target columns per patch of the multi-output entry points (pmk_model_set_targets_multi) */
+#define PMK_BLOCK_MAX_MEMBERS 4096  /* items of one (region, group) aggregate of pmk_query_items_block */
 #define PMK_COV_MAX_QUERIES 16384   /* queries of a batch whose joint covariance is asked for (pmk_query_items_cov) */
 #define PMK_REMOVE_MAX_ROWS 32   /* rows one patch can lose in one call (pmk_model_remove) */
 
@@ -648,6 +649,55 @@ int  pmk_query_items_cov_multi(pmk_query *q, const pmk_kernel_desc *th);
 int  pmk_predict_mixture_cov_multi_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
                                           double radius, double delta, double *Yq, int64_t ldyq, double *Vq, double *Cov,
                                           int64_t ldc);
+
+/* ---- block kriging: mean and kriging variance of weighted sums of the field over groups of queries --------------------
+ * Query j belongs to group[j] in [0, F), NON-DECREASING in j (the queries of a group are contiguous; a group may have no
+ * query), and carries the coefficient a[j] (any sign, zeros allowed).  With w_i = a_{j(i)} wn_i, wn the normalised weights
+ * of pmk_query_mix, the items of one (region r, group f) pair, an aggregate -- a run of the sorted item list -- give
+ *   kbar = sum_i w_i k_r(X_r, x_i),   Vbar = L_r^-1 kbar                       one column of the strip sweep
+ *   kappa = sum_{i,i'} w_i w_i' k_r(x_i, x_i') + sum_i w_i^2 addend_{j(i)}      (pmk_query_set_diag)
+ *   zbar = sum_i w_i z_i,  z_i = L_G^-1 (h(x_i) - C_H^T k_r(X_r, x_i))          under a trend with q > 0
+ *   s_{r,f} = max(kappa - |Vbar|^2, min_v sum_i w_i^2) + |zbar|^2               the trend's term after the floor
+ *   Vb[f] = sum_r s_{r,f}          Yb[f, c] = sum over the items i of f: w_i u_{i,c},  c < R
+ * which is a^T Cov a and a^T Yq of pmk_query_items_cov_multi + pmk_query_mix_cov by bilinearity, the cross term of a query
+ * that holds two items of one region included; a group of one query with a = 1 answers that query's Vq and Yq up to
+ * rounding.  Nothing of size Nq^2 or m_r^2 is allocated and a group of g points costs one swept column per region it
+ * touches, not g: the batch is not limited by PMK_COV_MAX_QUERIES.
+ * Order of operations.  w_i = a_j (blend weight / weight sum).  An entry of kbar is one chain of fused multiply-adds from
+ * 0 over the members in ascending sorted-item order, in the model's element type, so a column has the same bits whatever
+ * shares its strip; |Vbar|^2 is summed as the strip kernel of pmk_query_items sums |V|^2.  kappa: lane l of a wave takes the
+ * members i' = l, l + 64, .. and with each the members i <= i' (off-diagonal pairs twice), one chain; 64 partial sums meet
+ * in a fixed butterfly.  Yb, zbar and |zbar|^2 are chains of fused multiply-adds from 0 in item, member and basis order;
+ * Vb adds s at the first item of every aggregate, in item order.  A group's results depend on the group's queries alone.
+ * A group that blends an item of a patch with info != 0 or a flagged trend is NaN in Yb and Vb, the others keep their bits;
+ * an empty group answers 0 and +0.  Memory, owned by the query, grow only: 24 bytes per item, 12 per query, 56 per
+ * aggregate, 8 (R + 2) per group; the strip workspace is the model's.  Stage timer "items_block".
+ * Out of scope: the covariance between groups, non-contiguous groups, the sharded and all-gather exchanges, gradients of
+ * block quantities. */
+/* after pmk_query_items_multi / _multi_fitted on the current plan.  th: the kernel given to the items call, NULL for the
+ * model's own; weight_th: the blending profile; group [Nq] and a [Nq]: host arrays; want_var = 0 runs the weights and the
+ * mean reduction only.  Blocks (the aggregate count comes back to the host).  Before any launch: -1: no plan or no
+ * resident factor; -2: the last items are not those of pmk_query_items_multi / _multi_fitted or were taken under another
+ * trend, a query of explicit items, unknown family, PMK_MODSQEXP with D > 1, a Brownian-bridge blending profile; -3: the
+ * multi-output weights are stale (pmk_model_solve_multi), th NULL on a model without kernels, the model does not hold
+ * every leaf, or group decreases or leaves [0, F) (the text names the first offending j); -100: an allocation failed
+ * (the text gives the bytes asked for).  After the aggregate list and before the sweep: -5: an aggregate of more than
+ * PMK_BLOCK_MAX_MEMBERS items (the text names group and region).  New items and a new plan discard the results. */
+int  pmk_query_items_block(pmk_query *q, const pmk_kernel_desc *th, const pmk_kernel_desc *weight_th, int64_t F,
+                           const int32_t *group, const double *a, int want_var);
+/* Yb: F x R column-major with ldyb >= F; Vb: F.  Either may be NULL.  -2: before pmk_query_items_block; -3: Vb after
+ * want_var = 0; -4: ldyb < F.  _dev: device pointers, enqueues only. */
+int  pmk_query_fetch_block(pmk_query *q, double *Yb, int64_t ldyb, double *Vb);
+int  pmk_query_fetch_block_dev(pmk_query *q, double *Yb_dev, int64_t ldyb, double *Vb_dev);
+/* blocks.  The aggregates in the order of the sorted items: n their number, and per aggregate the global region, the
+ * group, the first sorted item, the member count, kappa, |Vbar|^2, |zbar|^2 and sum w^2.  Every pointer may be NULL (call
+ * once for n).  -1: no plan; -2: pmk_query_items_block has not run with want_var = 1 on the current items. */
+int  pmk_query_get_items_block(pmk_query *q, int64_t *n, int32_t *region, int32_t *group, int64_t *first, int32_t *count,
+                               double *kappa, double *vnorm2, double *znorm2, double *sw2);
+/* one-shot: create + plan + pmk_query_items_multi_fitted(0) + pmk_query_items_block(NULL, ..., Vb != NULL) + the fetch */
+int  pmk_predict_mixture_block_fitted(pmk_model *m, const pmk_kernel_desc *weight_th, int64_t Nq, const double *Xq,
+                                      double radius, double delta, int64_t F, const int32_t *group, const double *a,
+                                      double *Yb, int64_t ldyb, double *Vb);
 
 /* ---- posterior draws from the region blocks: no Nq x Nq covariance ---------------------------------------------------
  * The patches are independent GPs, so with S_r = L_r L_r^T the region blocks of pmk_query_items_cov(_multi),

@@ -22,7 +22,7 @@ export RKHSProblemType, fitRKHS!, query!, constructkernelmatrix, evalkernel, eva
        logevidencemixtureGP, logevidencemixtureGPmulti, loomixtureGP, loomixtureGPmulti,
        settrendmixtureGP!, trendmixtureGP, trendinfomixtureGP,
        selectmixtureGP!, selectcandidates, loomixtureGP_blend, loomixtureGP_blend_multi, selectblendGP_multi!,
-       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, querymixtureGP_cov_multi, samplemixtureGP_blocks, appendmixtureGP!, capacitymixtureGP,
+       querymixtureGP_grad, querymixtureGP_vgrad, querymixtureGP_cov, querymixtureGP_cov_multi, querymixtureGP_block, samplemixtureGP_blocks, appendmixtureGP!, capacitymixtureGP,
        removemixtureGP!, removablemixtureGP, reservemixtureGP!
 
 # ------------------------------------------------------------------------------------------ errors
@@ -1244,6 +1244,50 @@ function querymixtureGP_cov_multi(Xq::Vector{Vector{Float64}}, η::MixtureGPType
               "pmk_query_fetch_multi")
         check(ccall((:pmk_query_fetch_cov, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), q[], Cov, max(Nq, 1)), "pmk_query_fetch_cov")
         return Yq, Vq, Cov
+    finally
+        ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
+    end
+end
+
+"""querymixtureGP_block(Xq, group, a, η, root, levels, radius, δ, weight_θ; variance = true, staged = false) -> (Yb, Vb):
+block kriging (change of support).  Yb (F x R) is the prediction of sum_j a[j] f(x_j) over the queries j of every group and
+Vb (F) its kriging variance, for the columns of fitmixtureGPmulti! with the trend of settrendmixtureGP! if one is set
+(pmk_predict_mixture_block_fitted).  group[j] in 1:F is NON-DECREASING in j: the queries of a group are contiguous, a group
+may be empty; F = group[end].  a[j] is any real.  Vb is a' Cov a of querymixtureGP_cov_multi without the Nq x Nq matrix and
+without its limit of 16384 queries.  variance = false returns (Yb, nothing).  staged = true runs the staged calls
+(pmk_query_items_block); the results are the same."""
+function querymixtureGP_block(Xq::Vector{Vector{Float64}}, group::Vector{<:Integer}, a::Vector{Float64},
+                              η::MixtureGPType{Float64}, root, levels, radius::Float64, δ::Float64, weight_θ;
+                              variance::Bool = true, staged::Bool = false)
+    η.model == C_NULL && throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_block"))
+    R = η.R_multi
+    R >= 1 || throw(PMKError("fitmixtureGPmulti! must run before querymixtureGP_block"))
+    Nq = length(Xq); Xm = array2matrix(Xq)
+    (length(group) == Nq && length(a) == Nq) || throw(ArgumentError("one group and one coefficient per query point"))
+    g0 = Int32.(group .- 1)
+    F = Nq == 0 ? 0 : Int(group[end])
+    Yb = Matrix{Float64}(undef, F, R); Vb = Vector{Float64}(undef, F)
+    vptr = variance ? pointer(Vb) : Ptr{Float64}(C_NULL)
+    check(ccall((:pmk_model_set_bsp, libpmk), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), η.model, native(root), 0), "pmk_model_set_bsp")
+    if !staged
+        GC.@preserve Vb check(ccall((:pmk_predict_mixture_block_fitted, libpmk), Cint,
+                    (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Ptr{Float64}, Float64, Float64, Int64, Ptr{Int32}, Ptr{Float64},
+                     Ptr{Float64}, Int64, Ptr{Float64}),
+                    η.model, Ref(desc(weight_θ)), Nq, Xm, radius, δ, F, g0, a, Yb, max(F, 1), vptr),
+              "pmk_predict_mixture_block_fitted")
+        return Yb, (variance ? Vb : nothing)
+    end
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmk_query_create, libpmk), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), η.model, Nq, Xm, q), "pmk_query_create")
+    try
+        check(ccall((:pmk_query_plan, libpmk), Cint, (Ptr{Cvoid}, Float64, Float64), q[], radius, δ), "pmk_query_plan")
+        check(ccall((:pmk_query_items_multi_fitted, libpmk), Cint, (Ptr{Cvoid}, Cint), q[], 0), "pmk_query_items_multi_fitted")
+        check(ccall((:pmk_query_items_block, libpmk), Cint,
+                    (Ptr{Cvoid}, Ptr{KernelDesc}, Ref{KernelDesc}, Int64, Ptr{Int32}, Ptr{Float64}, Cint),
+                    q[], Ptr{KernelDesc}(C_NULL), Ref(desc(weight_θ)), F, g0, a, variance ? 1 : 0), "pmk_query_items_block")
+        GC.@preserve Vb check(ccall((:pmk_query_fetch_block, libpmk), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
+                    q[], Yb, max(F, 1), vptr), "pmk_query_fetch_block")
+        return Yb, (variance ? Vb : nothing)
     finally
         ccall((:pmk_query_destroy, libpmk), Cvoid, (Ptr{Cvoid},), q[])
     end

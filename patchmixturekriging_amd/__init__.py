@@ -20,7 +20,7 @@ from .mixture import (DeviceModel, DeviceQuery, MixtureGPDebugType, MixtureGPTyp
                       querymixtureGP_multi_patches, select_candidates, selectmixtureGP_, fitmixtureGP_trend_,
                       TrendRankException, loomixtureGP_blend, selectblendGP_, loomixtureGP_blend_multi,
                       selectblendGP_multi_, querymixtureGP_grad, querymixtureGP_cov, samplemixtureGP,
-                      querymixtureGP_cov_multi, samplemixtureGP_multi,
+                      querymixtureGP_cov_multi, samplemixtureGP_multi, querymixtureGP_block,
                       appendmixtureGP_, removemixtureGP_, reservemixtureGP_)
 from .partition import (BinaryNode, HyperplaneType, PartitionDataType, array2matrix,  # noqa: F401
                         convert2itpindex, fetchhyperplanes, findneighbourpartitions, findpartition,

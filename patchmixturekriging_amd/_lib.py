@@ -198,6 +198,12 @@ SIGNATURES = {
     "pmk_query_draw": (C.c_int, [_vp, _kp, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "pmk_predict_mixture_cov_multi_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, _dp, C.c_int64,
                                                        _dp, _dp, C.c_int64]),
+    "pmk_query_items_block": (C.c_int, [_vp, _kp, _kp, C.c_int64, _i32p, _dp, C.c_int]),
+    "pmk_query_fetch_block": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
+    "pmk_query_fetch_block_dev": (C.c_int, [_vp, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pmk_query_get_items_block": (C.c_int, [_vp, _ip, _i32p, _i32p, _ip, _i32p, _dp, _dp, _dp, _dp]),
+    "pmk_predict_mixture_block_fitted": (C.c_int, [_vp, _kp, C.c_int64, _dp, C.c_double, C.c_double, C.c_int64, _i32p, _dp,
+                                                   _dp, C.c_int64, _dp]),
     "pmk_model_capacity": (C.c_int, [_vp, _ip]),
     "pmk_model_append": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, _i32p, _ip]),
     "pmk_model_removable": (C.c_int, [_vp, _ip]),

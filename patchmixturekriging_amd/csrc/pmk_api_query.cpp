@@ -116,16 +116,6 @@ static int download_item_rows(pmk_query *q, const double *d_src, size_t ld, size
     return 0;
 }
 
-// the blending profile of pmk_query_mix / _mix_multi: a stationary kernel
-static int blend_profile_ok(const pmk_kernel_desc *weight_th, const char *who)
-{
-    if (!kernel_ok(weight_th) || weight_th->family >= PMK_BB10) {
-        set_error("%s: the blending profile must be a stationary kernel (evalkernel(tau, theta))", who);
-        return -2;
-    }
-    return 0;
-}
-
 static int query_range_ok(const pmk_query *q, int64_t q0, int64_t q1, const char *who)
 {
     if (q0 < 0 || q1 > q->Nq || q0 > q1) { set_error("%s: bad query range", who); return -3; }
@@ -286,6 +276,9 @@ void pmk_query_destroy(pmk_query *q)
     dev_free(q->d_cov_f); dev_free(q->d_fdesc); dev_free(q->d_forder); dev_free(q->d_ftasks); dev_free(q->d_finfo);
     dev_free(q->d_fact); dev_free(q->d_fjit); dev_free(q->d_frel); dev_free(q->d_draw_t); dev_free(q->d_draw_z);
     dev_free(q->d_draw_e);
+    dev_free(q->d_blk_group); dev_free(q->d_blk_a); dev_free(q->d_blk_gq); dev_free(q->d_blk_w); dev_free(q->d_blk_head);
+    dev_free(q->d_blk_agg_of); dev_free(q->d_blk_scan); dev_free(q->d_blk_aggs); dev_free(q->d_blk_piece);
+    dev_free(q->d_blk_tasks); dev_free(q->d_blk_aoff); dev_free(q->d_blk_y); dev_free(q->d_blk_v);
     dev_free(q->d_loo_x);              // base of the leave-one-out arena (loo_reserve)
     pmk_query_destroy(q->loo_inner);
     delete q;
@@ -997,18 +990,6 @@ int pmk_predict_mixture_vgrad_fitted(pmk_model *m, const pmk_kernel_desc *weight
 
 // ------------------------------------------------------------------------------------------ joint covariance of the batch
 static const char COV_NEEDS_ALL[] = "the joint covariance needs a model that holds every leaf";
-
-// a kernel the covariance stages evaluate: any family, ModSqExp only at D = 1 (nothing here differentiates, so the
-// Brownian-bridge families are admitted)
-static int cov_kernel_ok(const pmk_kernel_desc *th, int D, const char *who, const char *role)
-{
-    if (!kernel_ok(th)) { set_error("%s: unknown kernel family (%s)", who, role); return -2; }
-    if (th->family == PMK_MODSQEXP && D > 1) {
-        set_error("%s: %s is PMK_MODSQEXP, which is defined for D = 1 only (D = %d)", who, role, D);
-        return -2;
-    }
-    return 0;
-}
 
 static int cov_batch_ok(int64_t Nq, const char *who)
 {

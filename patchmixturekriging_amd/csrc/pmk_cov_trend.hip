@@ -78,6 +78,18 @@ __global__ __launch_bounds__(256) void cov_trend_flags_kernel(int64_t P, const i
     if (r < P) flags[r] = patch_is_bad(info, tinfo, r) ? 1 : 0;
 }
 
+// Z alone, for the callers that need no block (pmk_query_items_block): the same kernel on the same arguments
+int launch_cov_trend_items(pmk_query *q, hipStream_t s)
+{
+    const pmk_model *m = q->m;
+    if (q->total == 0) return 0;
+    hipLaunchKernelGGL(cov_trend_items_kernel, grid256(q->total), dim3(256), 0, s, q->total, q->d_sorted_item,
+                       q->d_item_region, q->d_item_query, q->d_xq, m->D, q->R_items, m->trend_q, q->um_ld, m->d_tL, q->d_um,
+                       q->d_cov_z);
+    PMK_HIP(hipGetLastError());
+    return 0;
+}
+
 // after launch_items_cov on the same stream; the tasks, the pairs, Z and the flags are the caller's
 // (pmk_query_items_cov_multi)
 int launch_cov_trend(pmk_query *q, hipStream_t s)

@@ -21,6 +21,28 @@ inline bool kernel_ok(const pmk_kernel_desc *th)
     }
 }
 
+// the blending profile of pmk_query_mix / _mix_multi: a stationary kernel
+inline int blend_profile_ok(const pmk_kernel_desc *weight_th, const char *who)
+{
+    if (!kernel_ok(weight_th) || weight_th->family >= PMK_BB10) {
+        set_error("%s: the blending profile must be a stationary kernel (evalkernel(tau, theta))", who);
+        return -2;
+    }
+    return 0;
+}
+
+// a kernel the covariance stages evaluate: any family, ModSqExp only at D = 1 (nothing here differentiates, so the
+// Brownian-bridge families are admitted)
+inline int cov_kernel_ok(const pmk_kernel_desc *th, int D, const char *who, const char *role)
+{
+    if (!kernel_ok(th)) { set_error("%s: unknown kernel family (%s)", who, role); return -2; }
+    if (th->family == PMK_MODSQEXP && D > 1) {
+        set_error("%s: %s is PMK_MODSQEXP, which is defined for D = 1 only (D = %d)", who, role, D);
+        return -2;
+    }
+    return 0;
+}
+
 template <typename T>
 int dev_alloc(T **p, int64_t count)
 {
@@ -148,6 +170,7 @@ inline void reset_item_state(pmk_query *q)
     q->mixed_multi = false;
     q->items_fn = q->grad_items = q->mixed_grad = false;
     q->vgrad_items = q->mixed_vgrad = false;
+    q->block_items = q->block_var = false;
     // blocks with a trend's term (pmk_query_items_cov_multi) were computed from the item rows that now go
     if (q->cov_trend_q > 0) {
         q->cov_items = q->mixed_cov = q->cov_factored = false;

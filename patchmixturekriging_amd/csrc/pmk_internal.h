@@ -99,6 +99,22 @@ struct CovTask {
 };
 struct CovPair { int32_t ta, tb; };   // two strips of one region, ta <= tb
 
+// Block kriging (pmk_block.hip).  An aggregate: the sorted items [first, first + count) of one region that belong to one
+// group of queries, built on the device.  A task: up to TQ consecutive aggregates of one region, dealt over the region's
+// strips as build_strip_tasks deals items, built on the host from the regions' first aggregates.
+struct BlockAgg {
+    int32_t region;   // local patch
+    int32_t group;    // the queries' group
+    int64_t first;    // first sorted item
+    int32_t count;    // members (<= PMK_BLOCK_MAX_MEMBERS)
+    int32_t pad_;
+};
+struct BlockTask {
+    int32_t region;   // local patch
+    int32_t count;    // aggregates of the strip (<= TQ)
+    int64_t first;    // first aggregate of the strip
+};
+
 // A region block and its Cholesky factor (pmk_draw.hip).  The factor is padded to nt tiles of DRAW_TILE rows, column-major
 // with leading dimension DRAW_TILE nt, the identity in the padding.  Built on the host from the plan's region offsets.
 constexpr int DRAW_TILE = 32;
@@ -340,6 +356,19 @@ struct pmk_query {
     double *d_draw_t = nullptr; int64_t draw_t_cap = 0;           // total x (draw chunk): T_r = L_r Z_r in sorted-item order
     double *d_draw_z = nullptr; int64_t draw_z_cap = 0;           // device copy of a chunk of host z
     double *d_draw_e = nullptr; int64_t draw_e_cap = 0;           // a chunk of E for a host pointer
+    // block kriging (pmk_query_items_block, pmk_block.hip).  block_items: it has run on the current items; block_var: with
+    // the variance, so the aggregates and their pieces are there.  New items or a new plan discard both.  Grow only.
+    bool block_items = false, block_var = false;
+    int64_t blk_F = 0, blk_naggs = 0, blk_ntasks = 0, blk_grid = 0;
+    int32_t *d_blk_group = nullptr; double *d_blk_a = nullptr; int64_t blk_q_cap = 0;      // Nq: group and coefficient
+    int64_t *d_blk_gq = nullptr; int64_t blk_gq_cap = 0;                                   // F + 1: first query of a group
+    double *d_blk_w = nullptr; int32_t *d_blk_head = nullptr, *d_blk_agg_of = nullptr;     // per sorted item: weight, head
+    int64_t *d_blk_scan = nullptr; int64_t blk_item_cap = 0;                               //   flag, aggregate; scan of the heads
+    pmk::BlockAgg *d_blk_aggs = nullptr; double *d_blk_piece = nullptr; int64_t blk_agg_cap = 0;   // pieces: kappa, |Vbar|^2, |zbar|^2, sum w^2 (blk_agg_cap each)
+    pmk::BlockTask *d_blk_tasks = nullptr; int64_t blk_tasks_cap = 0;
+    int64_t *d_blk_aoff = nullptr; int64_t blk_aoff_cap = 0;                               // P + 2: first aggregate of a region, then the cap's offender
+    double *d_blk_y = nullptr; int64_t blk_y_cap = 0;                                      // F x R column-major
+    double *d_blk_v = nullptr; int64_t blk_v_cap = 0;                                      // F
     double min_v = 1e-12;           // floor of the predictive variance (queryinner!'s keyword min_v, mixtureGP.jl:296)
     // blended leave-one-out (pmk_query_items_loo, pmk_loo_mix.hip): non-member marks and their exclusive scan over the
     // sorted items, the compacted requests (points, regions, addends) and their results, ONE allocation with d_loo_x as
@@ -393,6 +422,7 @@ inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
     int launch_items_grad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                   \
     int launch_items_vgrad(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
     int launch_items_cov(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                    \
+    int launch_items_block(pmk_query *q, const pmk_kernel_desc *th, hipStream_t s);                                  \
     int launch_append_border(pmk_model *m, const pmk_query *q, const double *d_y, const double *d_diag, hipStream_t s); \
     int set_append_attributes();                                                                                     \
     int launch_remove_rows(pmk_model *m, const RemoveTask *d_tasks, int64_t ntasks, const int32_t *d_rows,           \
@@ -425,6 +455,11 @@ int launch_trend_vgrad(pmk_query *q, hipStream_t s);
 int launch_mix_vgrad(pmk_query *q, const pmk_kernel_desc &wth, int64_t q0, int64_t q1, hipStream_t s);
 int launch_mix_cov(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s);
 int launch_cov_trend(pmk_query *q, hipStream_t s);
+int launch_cov_trend_items(pmk_query *q, hipStream_t s);
+int launch_block_weights(pmk_query *q, const pmk_kernel_desc &wth, hipStream_t s);
+int launch_block_heads(pmk_query *q, hipStream_t s);
+int launch_block_aggregates(pmk_query *q, int cap, unsigned long long *d_over, int64_t *d_aoff, hipStream_t s);
+int launch_block_reduce(pmk_query *q, bool want_var, int qt, hipStream_t s);
 int launch_factor_cov(pmk_query *q, int have_factors, hipStream_t s);
 int launch_draw(pmk_query *q, const pmk_kernel_desc &wth, const double *d_z, int64_t ldz, int64_t n, double *d_E,
                 int64_t lde, hipStream_t s);

@@ -40,6 +40,7 @@ static int no_gpu(const char *what)
     int launch_items_grad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_grad"); } \
     int launch_items_vgrad(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_vgrad"); } \
     int launch_items_cov(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_cov"); }  \
+    int launch_items_block(pmk_query *, const pmk_kernel_desc *, hipStream_t) { return no_gpu("launch_items_block"); } \
     int launch_append_border(pmk_model *, const pmk_query *, const double *, const double *, hipStream_t) { return no_gpu("launch_append_border"); } \
     int set_append_attributes() { return 0; }                                                                       \
     int launch_remove_rows(pmk_model *, const RemoveTask *, int64_t, const int32_t *, hipStream_t) { return no_gpu("launch_remove_rows"); } \
@@ -64,6 +65,11 @@ int launch_trend_vgrad(pmk_query *, hipStream_t) { return no_gpu("launch_trend_v
 int launch_mix_vgrad(pmk_query *, const pmk_kernel_desc &, int64_t, int64_t, hipStream_t) { return no_gpu("launch_mix_vgrad"); }
 int launch_mix_cov(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_mix_cov"); }
 int launch_cov_trend(pmk_query *, hipStream_t) { return no_gpu("launch_cov_trend"); }
+int launch_cov_trend_items(pmk_query *, hipStream_t) { return no_gpu("launch_cov_trend_items"); }
+int launch_block_weights(pmk_query *, const pmk_kernel_desc &, hipStream_t) { return no_gpu("launch_block_weights"); }
+int launch_block_heads(pmk_query *, hipStream_t) { return no_gpu("launch_block_heads"); }
+int launch_block_aggregates(pmk_query *, int, unsigned long long *, int64_t *, hipStream_t) { return no_gpu("launch_block_aggregates"); }
+int launch_block_reduce(pmk_query *, bool, int, hipStream_t) { return no_gpu("launch_block_reduce"); }
 int launch_factor_cov(pmk_query *, int, hipStream_t) { return no_gpu("launch_factor_cov"); }
 int launch_draw(pmk_query *, const pmk_kernel_desc &, const double *, int64_t, int64_t, double *, int64_t, hipStream_t)
 {

@@ -1018,6 +1018,72 @@ class DeviceQuery:
                    "pmk_query_get_items_cov")
         return idx[:m.value], S[:m.value, :m.value]
 
+    # ---- block kriging: weighted sums over groups of queries (pmk_block.hip)
+    def items_block(self, group, a, weight_theta, F=None, theta=None, variance=True):
+        """pmk_query_items_block: mean and kriging variance of sum_j a[j] f(x_j) over the queries j of every group, after
+        items_multi / items_multi_fitted on this plan.  group: int32 per query in [0, F), non-decreasing (the queries of a
+        group are contiguous, a group may be empty); a: one coefficient per query; F: the number of groups (default: the
+        last group + 1); theta: the kernel given to the items call, or (None) the model's own.  variance=False runs the
+        weights and the mean reduction only.  Closure-carrying kernels raise TypeError before any device call."""
+        _refuse_closure_kernel(weight_theta, "items_block")
+        g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if len(g) != self.Nq or len(c) != self.Nq:
+            raise ValueError("one group and one coefficient per query point (%d), not %d and %d" % (self.Nq, len(g), len(c)))
+        if F is None:
+            F = int(g[-1]) + 1 if len(g) else 0
+        if theta is None:
+            if not getattr(self.model, "_has_kernels", False):
+                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+            ptr = None
+        else:
+            _refuse_closure_kernel(theta, "items_block")
+            d = theta.desc()
+            ptr = C.byref(d)
+        w = weight_theta.desc()
+        _lib.check(self.L.pmk_query_items_block(self.h, ptr, C.byref(w), int(F), g.ctypes.data_as(C.POINTER(C.c_int32)), _d(c),
+                                                int(bool(variance))), "pmk_query_items_block")
+        self.block_F, self.block_variance = int(F), bool(variance)
+
+    def fetch_block(self):
+        """(Yb [F, R], Vb [F] or None after variance=False)"""
+        F, R = getattr(self, "block_F", 0), int(getattr(self, "R_items", 0))
+        Vb = np.empty(F) if getattr(self, "block_variance", False) else None
+        buf = np.empty((max(F, 1), max(R, 1)), order="F")
+        _lib.check(self.L.pmk_query_fetch_block(self.h, _d(buf), max(F, 1), None if Vb is None else _d(Vb)),
+                   "pmk_query_fetch_block")
+        return np.asfortranarray(buf[:F, :R]), Vb
+
+    def fetch_block_into(self, Yb, Vb=None):
+        """pmk_query_fetch_block_dev: Yb is a device array (F, R) in column-major order (its column stride is the leading
+        dimension); Vb (F) only if items_block ran with the variance"""
+        F, R = getattr(self, "block_F", 0), int(getattr(self, "R_items", 0))
+        ya = self._device_out(Yb, "Yb")
+        if len(ya.shape) != 2 or ya.shape != (F, R):
+            raise ValueError("Yb must have shape (%d, %d), not %s" % (F, R, ya.shape))
+        _, ld = ya.columns(F)
+        if Vb is not None and not getattr(self, "block_variance", False):
+            raise ValueError("Vb was not computed: items_block ran mean-only (variance=False)")
+        va = None if Vb is None else self._device_out(Vb, "Vb").vector(F)
+        _lib.check(self.L.pmk_query_fetch_block_dev(self.h, ya.ptr, ld, None if va is None else va.ptr),
+                   "pmk_query_fetch_block_dev")
+
+    def item_blocks(self):
+        """pmk_query_get_items_block -> dict of arrays, one entry per (region, group) aggregate in sorted-item order:
+        region, group, first (sorted item), count, kappa, vnorm2 (|Vbar|^2), znorm2 (|zbar|^2), sw2 (sum w^2)"""
+        n = C.c_int64()
+        _lib.check(self.L.pmk_query_get_items_block(self.h, C.byref(n), None, None, None, None, None, None, None, None),
+                   "pmk_query_get_items_block")
+        k = max(n.value, 1)
+        i32 = lambda: np.empty(k, dtype=np.int32)
+        out = dict(region=i32(), group=i32(), first=np.empty(k, dtype=np.int64), count=i32(), kappa=np.empty(k),
+                   vnorm2=np.empty(k), znorm2=np.empty(k), sw2=np.empty(k))
+        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.pmk_query_get_items_block(self.h, None, p32(out["region"]), p32(out["group"]), _i(out["first"]),
+                                                    p32(out["count"]), _d(out["kappa"]), _d(out["vnorm2"]),
+                                                    _d(out["znorm2"]), _d(out["sw2"])), "pmk_query_get_items_block")
+        return {key: v[:n.value] for key, v in out.items()}
+
     # ---- posterior draws from the region blocks (pmk_draw.hip)
     def items_cov_blocks(self, theta=None, multi=False):
         """pmk_query_items_cov_blocks: the region blocks of items_cov (multi=False) or items_cov_multi (multi=True) for a
@@ -1892,6 +1958,25 @@ def querymixtureGP_cov_multi(Xq, eta, root, levels, radius, delta, weight_theta)
     q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, "querymixtureGP_cov_multi")
     Yq, Vq = q.fetch_multi(q.model.R)
     return Yq, Vq, q.fetch_cov()
+
+
+def querymixtureGP_block(Xq, group, a, eta, root, levels, radius, delta, weight_theta, variance=True):
+    """block kriging (change of support) -> (Yb [F, R], Vb [F] or None): the prediction of sum_j a[j] f(x_j) over the
+    queries j of every group and its kriging variance, for the R columns of fitmixtureGP_multi_ or fitmixtureGP_trend_
+    (list-built and from_tree etas).  group: int per query, non-decreasing from 0 (F = group[-1] + 1); a: one coefficient
+    per query.  A block average over g points is a = 1 / g, an integral takes quadrature weights, a contrast mixes signs.
+    Vb is a^T Cov a of querymixtureGP_cov_multi without the Nq x Nq matrix and without its limit of 16384 queries.
+    Closure-carrying kernels raise TypeError before any device call."""
+    who = "querymixtureGP_block"
+    _refuse_closure_kernel(weight_theta, who)
+    theta = getattr(getattr(eta, "_model", None), "theta", None)
+    if theta is not None:
+        _refuse_closure_kernel(theta, who)
+    q = _patches_query(Xq, eta, root, radius, delta, who)
+    q.model._need(multi=True)
+    q.items_multi_fitted(False)
+    q.items_block(group, a, weight_theta, variance=variance)
+    return q.fetch_block()
 
 
 def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None,
