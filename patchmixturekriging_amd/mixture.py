@@ -26,6 +26,15 @@ def _i(a):
     return a.ctypes.data_as(_ip)
 
 
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _dps(arrays, P):
+    """the array of P pointers to a list of float64 arrays (one per patch)"""
+    return (_dp * P)(*[_d(a) for a in arrays])
+
+
 class GlobalArray:
     """a float64 array of all points, on the host (numpy) or on the device (anything with __cuda_array_interface__, such
     as a torch tensor): address, shape and strides in elements, validated without any device call.  `keep` holds the
@@ -114,10 +123,40 @@ class PosDefException(np.linalg.LinAlgError):
 class DeviceModel:
     """pmk_model: the fitted per-patch factors, resident on the GPU"""
 
+    # The mirror of the library's model state (include/pmk.h), so that a call in the wrong state is refused before any
+    # device call.  These are the values of a model just created from points; every birth path (the constructor,
+    # from_tree, a test's object.__new__) sets only what differs, and only the calls named here change them.
+    _from_tree = False      # built by from_tree: the *_global calls serve it, append / remove take their _global forms
+    _all_leaves = False     # from_tree: the model holds every leaf of its tree, not a shard (blended leave-one-out)
+    _has_factor = False     # a factor is resident: fit, fit_patches, from_factors; new targets or addends drop it
+    _has_targets = True     # the model holds y: False only on a model built by from_factors
+    _has_kernels = False    # the kernels of the factor are known: fit, fit_patches, set_kernels
+    _loo_done = False       # loo() ran on the resident factor; a new factor and changed rows make it stale
+    _multi_solved = False   # solve_multi ran on it; stale after a new factor, changed rows, new R columns, set_trend
+    R = 0                   # the columns of set_targets_multi(_global); changed rows (reserve, append, remove) discard them
+    _X = None               # X: the points of every patch (from_tree: cut from _X_global on first use)
+    _X_global = None        # from_tree on a host array: that array, extended by append_global
+    _index = None           # patch_index() of a from_tree model, read back once; append_global and remove_global reset it
+    theta = None            # of the last fit(); None after fit_patches (thetas, sigma2s then)
+    sigma2 = None
+
+    def _new_factor(self):
+        """fit, fit_patches: the factor, z and c are those of the kernels given; d and the multi-output weights are stale"""
+        self._has_factor = self._has_targets = self._has_kernels = True
+        self._loo_done = self._multi_solved = False
+
+    def _rows_changed(self):
+        """reserve, append, remove: loo() is stale and the multi-output targets are discarded (set_targets_multi again)"""
+        self._loo_done = self._multi_solved = False
+        self.R = 0
+
+    def _targets_replaced(self):
+        """set_targets(_global), set_diag(_global): the resident factor no longer belongs to the model's y and addends"""
+        self._has_factor = False
+
     def __init__(self, X_parts, y_parts, ctx=None, _factors=None, dtype="f64"):
         self.ctx = ctx or default_context()
         L = self.ctx.L
-        self._from_tree = False
         self.X = [as_points(x) for x in X_parts]
         self.P = len(self.X)
         if self.P == 0:
@@ -128,30 +167,20 @@ class DeviceModel:
         for x, y in zip(self.X, ys):
             if x.shape[0] != len(y):
                 raise ValueError("length(c) == length(X) must hold per patch")     # mixtureGP.jl:298
-        PA = _dp * self.P
+        P = self.P
         h = C.c_void_p()
         self.dtype = dtype
         if _factors is None:
             # dtype "f32": fp32 storage + fp32 MFMA on the device (BASELINE config E); host buffers stay float64
-            _lib.check(L.pmk_model_create_ex(self.ctx.h, self.D, self.P, _i(self.n), PA(*[_d(x) for x in self.X]),
-                                             PA(*[_d(y) for y in ys]), {"f64": 0, "f32": 1}[dtype], C.byref(h)),
-                       "pmk_model_create")
+            _lib.check(L.pmk_model_create_ex(self.ctx.h, self.D, P, _i(self.n), _dps(self.X, P), _dps(ys, P),
+                                             {"f64": 0, "f32": 1}[dtype], C.byref(h)), "pmk_model_create")
         else:
             Ls = [np.asfortranarray(l, dtype=np.float64) for l in _factors]
             ldl = np.array([l.shape[0] for l in Ls], dtype=np.int64)
-            _lib.check(L.pmk_model_load(self.ctx.h, self.D, self.P, _i(self.n), PA(*[_d(x) for x in self.X]),
-                                        PA(*[_d(y) for y in ys]), PA(*[_d(l) for l in Ls]), _i(ldl), C.byref(h)),
-                       "pmk_model_load")
+            _lib.check(L.pmk_model_load(self.ctx.h, self.D, P, _i(self.n), _dps(self.X, P), _dps(ys, P), _dps(Ls, P),
+                                        _i(ldl), C.byref(h)), "pmk_model_load")
+            self._has_factor, self._has_targets = True, False       # factors but no y and no theta: set_kernels
         self.h = h
-        self.theta = None
-        self.sigma2 = None
-        # what the device model holds (mirrors the library's state rules, so that a call in the wrong state is
-        # refused before any device call)
-        self._has_factor = _factors is not None
-        self._has_targets = _factors is None
-        self._loo_done = False
-        self._multi_solved = False
-        self._has_kernels = False       # a fit records its kernels; a model built from factors needs set_kernels
 
     @classmethod
     def from_tree(cls, root, X, y=None, eps=None, ctx=None, dtype="f64", leaf_base=0, P=None, reserve=None):
@@ -180,17 +209,13 @@ class DeviceModel:
                                                {"f64": 0, "f32": 1}[dtype], C.byref(h)), "pmk_model_create_from_bsp")
         self.h = h
         self.dtype, self.D, self.N = dtype, xa.shape[1], N
-        self._from_tree, self._X, self._X_global = True, None, (None if xa.device else X)
+        self._from_tree, self._X_global = True, (None if xa.device else X)
         self.leaf_base = int(leaf_base)
         self._root, self._eps = root, (None if eps is None else float(eps))     # append_global assigns with them
         self.P = int(L.pmk_model_num_patches(h))
         self._all_leaves = self.leaf_base == 0 and self.P == int(L.pmk_bsp_num_leaves(nat.h))
-        self._index = None
         off, _ = self.patch_index()
         self.n = np.diff(off)
-        self.theta = self.sigma2 = None
-        self._has_factor, self._has_targets = False, True
-        self._loo_done = self._multi_solved = self._has_kernels = False
         if reserve is not None:
             self.reserve(reserve)
         return self
@@ -199,7 +224,7 @@ class DeviceModel:
     def X(self):
         """the points of every patch; on a model built by from_tree they are cut from the index list on first use, and
         only if X was a host array (None otherwise: the points never came to the host)"""
-        if self._X is None and getattr(self, "_X_global", None) is not None:
+        if self._X is None and self._X_global is not None:
             off, inds = self.patch_index()
             self._X = [self._X_global[inds[off[r]:off[r + 1]]] for r in range(self.P)]
         return self._X
@@ -209,7 +234,7 @@ class DeviceModel:
         self._X = value
 
     def _need_tree_model(self, who):
-        if not getattr(self, "_from_tree", False):
+        if not self._from_tree:
             raise _lib.PmkError("%s: the model was built from lists of patches, not by from_tree" % who)
 
     def patch_index(self):
@@ -230,7 +255,7 @@ class DeviceModel:
         self._need_tree_model("set_targets_global")
         ya = GlobalArray(y, "y").vector(self.N)
         _lib.check(self.ctx.L.pmk_model_set_targets_global(self.h, ya.ptr), "pmk_model_set_targets_global")
-        self._has_factor = False
+        self._targets_replaced()
 
     def set_targets_multi_global(self, Y):
         """pmk_model_set_targets_multi_global: Y is (N, R) column-major (Fortran order; its column stride is the leading
@@ -246,7 +271,7 @@ class DeviceModel:
         """pmk_model_set_diag_global: N addends of the kernel's diagonal through the index list (None clears it)"""
         self._need_tree_model("set_diag_global")
         da = None if diag is None else GlobalArray(diag, "diag").vector(self.N)
-        self._has_factor = False
+        self._targets_replaced()
         _lib.check(self.ctx.L.pmk_model_set_diag_global(self.h, None if da is None else da.ptr), "pmk_model_set_diag_global")
 
     @classmethod
@@ -270,13 +295,12 @@ class DeviceModel:
 
     def set_targets(self, y_parts):
         ys = [np.ascontiguousarray(y, dtype=np.float64) for y in y_parts]
-        PA = _dp * self.P
-        _lib.check(self.ctx.L.pmk_model_set_targets(self.h, PA(*[_d(y) for y in ys])), "pmk_model_set_targets")
-        self._has_factor = False
+        _lib.check(self.ctx.L.pmk_model_set_targets(self.h, _dps(ys, self.P)), "pmk_model_set_targets")
+        self._targets_replaced()
 
     def set_diag(self, diag_parts):
         """pmk_model_set_diag: per-point addend of the kernel's diagonal for the next fits (None clears it)"""
-        self._has_factor = False
+        self._targets_replaced()
         if diag_parts is None:
             _lib.check(self.ctx.L.pmk_model_set_diag(self.h, None), "pmk_model_set_diag")
             return
@@ -284,19 +308,16 @@ class DeviceModel:
         for d, n in zip(ds, self.n):
             if len(d) != n:
                 raise ValueError("one addend per point")
-        PA = _dp * self.P
-        _lib.check(self.ctx.L.pmk_model_set_diag(self.h, PA(*[_d(d) for d in ds])), "pmk_model_set_diag")
+        _lib.check(self.ctx.L.pmk_model_set_diag(self.h, _dps(ds, self.P)), "pmk_model_set_diag")
 
     def fit(self, theta, sigma2):
         """enqueue kernel build + Cholesky + solves for every patch"""
-        if getattr(self, "_from_tree", False):
+        if self._from_tree:
             _refuse_closure_kernel(theta, "fit")
         d = theta.desc()
         _lib.check(self.ctx.L.pmk_model_fit(self.h, C.byref(d), float(sigma2)), "pmk_model_fit")
         self.theta, self.sigma2 = theta, float(sigma2)
-        self._has_factor, self._has_targets = True, True
-        self._has_kernels = True
-        self._loo_done = self._multi_solved = False         # a new factor: d and the multi-output weights are stale
+        self._new_factor()
 
     def fit_patches(self, thetas, sigma2s):
         """pmk_model_fit_patches: the fit with one kernel and one noise variance PER PATCH (thetas[r], sigma2s[r] belong
@@ -305,9 +326,7 @@ class DeviceModel:
         _lib.check(self.ctx.L.pmk_model_fit_patches(self.h, descs, _d(s2)), "pmk_model_fit_patches")
         self.theta, self.sigma2 = None, None
         self.thetas, self.sigma2s = list(thetas), [float(v) for v in s2]
-        self._has_factor, self._has_targets = True, True
-        self._has_kernels = True
-        self._loo_done = self._multi_solved = False
+        self._new_factor()
 
     def set_kernels(self, thetas):
         """pmk_model_set_kernels: the kernels of a model built by from_factors (which holds factors but no theta), for
@@ -327,14 +346,13 @@ class DeviceModel:
 
     def info(self):
         info = np.zeros(self.P, dtype=np.int32)
-        _lib.check(self.ctx.L.pmk_model_info(self.h, info.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_model_info")
+        _lib.check(self.ctx.L.pmk_model_info(self.h, _i32(info)), "pmk_model_info")
         return info
 
     def weights(self):
         """c_set: the weights of every patch, one device-to-host transfer for the whole model"""
         out = [np.empty(int(n)) for n in self.n]
-        PA = _dp * self.P
-        _lib.check(self.ctx.L.pmk_model_get_weights(self.h, PA(*[_d(c) for c in out])), "pmk_model_get_weights")
+        _lib.check(self.ctx.L.pmk_model_get_weights(self.h, _dps(out, self.P)), "pmk_model_get_weights")
         return out
 
     def get(self, patch, what):
@@ -358,9 +376,8 @@ class DeviceModel:
         """pmk_model_set_targets_multi: R target columns per patch (Y_parts[r] is n_r x R, or a vector for R = 1)"""
         Ys = multi_targets(Y_parts, self.n)
         R = Ys[0].shape[1]
-        PA = _dp * self.P
         ldy = np.array([y.shape[0] for y in Ys], dtype=np.int64)
-        _lib.check(self.ctx.L.pmk_model_set_targets_multi(self.h, R, PA(*[_d(y) for y in Ys]), _i(ldy)),
+        _lib.check(self.ctx.L.pmk_model_set_targets_multi(self.h, R, _dps(Ys, self.P), _i(ldy)),
                    "pmk_model_set_targets_multi")
         self.R = R
         self._multi_solved = False
@@ -372,13 +389,12 @@ class DeviceModel:
 
     def weights_multi(self):
         """the n_r x R weights of every patch (one device-to-host transfer)"""
-        R = getattr(self, "R", 0)
+        R = self.R
         if R < 1:
             raise _lib.PmkError("set_targets_multi has not run on this model")
         out = [np.empty((int(n), R), order="F") for n in self.n]
-        PA = _dp * self.P
         ldc = np.array([int(n) for n in self.n], dtype=np.int64)
-        _lib.check(self.ctx.L.pmk_model_get_weights_multi(self.h, PA(*[_d(c) for c in out]), _i(ldc)),
+        _lib.check(self.ctx.L.pmk_model_get_weights_multi(self.h, _dps(out, self.P), _i(ldc)),
                    "pmk_model_get_weights_multi")
         return out
 
@@ -407,7 +423,7 @@ class DeviceModel:
         patch has fewer points than basis functions"""
         self._need(multi=True)
         flags = np.zeros(self.P, dtype=np.int32)
-        _lib.check(self.ctx.L.pmk_model_trend_info(self.h, flags.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_model_trend_info")
+        _lib.check(self.ctx.L.pmk_model_trend_info(self.h, _i32(flags)), "pmk_model_trend_info")
         return flags
 
     # ---- model selection from the resident factor (per patch: a point of several overlapping patches has a score in each)
@@ -447,9 +463,7 @@ class DeviceModel:
         mean is y_i - res_i), var_i = 1 / d_i (includes sigma2)"""
         self._need(loo=True)
         res, var = [np.empty(int(n)) for n in self.n], [np.empty(int(n)) for n in self.n]
-        PA = _dp * self.P
-        _lib.check(self.ctx.L.pmk_model_get_loo(self.h, PA(*[_d(a) for a in res]), PA(*[_d(a) for a in var])),
-                   "pmk_model_get_loo")
+        _lib.check(self.ctx.L.pmk_model_get_loo(self.h, _dps(res, self.P), _dps(var, self.P)), "pmk_model_get_loo")
         return res, var
 
     def loo_values_multi(self):
@@ -459,9 +473,8 @@ class DeviceModel:
         self._need(loo=True, multi=True)
         RES = [np.empty((int(n), self.R), order="F") for n in self.n]
         var = [np.empty(int(n)) for n in self.n]
-        PA = _dp * self.P
         ld = np.array([int(n) for n in self.n], dtype=np.int64)
-        _lib.check(self.ctx.L.pmk_model_get_loo_multi(self.h, PA(*[_d(a) for a in RES]), _i(ld), PA(*[_d(a) for a in var])),
+        _lib.check(self.ctx.L.pmk_model_get_loo_multi(self.h, _dps(RES, self.P), _i(ld), _dps(var, self.P)),
                    "pmk_model_get_loo_multi")
         return RES, var
 
@@ -487,8 +500,7 @@ class DeviceModel:
             raise ValueError("rows must be an int or %d ints, one per patch" % self.P)
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         _lib.check(self.ctx.L.pmk_model_reserve(self.h, _i(rows)), "pmk_model_reserve")
-        self._loo_done = self._multi_solved = False
-        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+        self._rows_changed()
         return self.capacity()
 
     def _need_appendable(self, who):
@@ -497,19 +509,17 @@ class DeviceModel:
             raise _lib.PmkError("%s: a model built from factors holds no targets: z cannot be extended" % who)
 
     def _append(self, x, y, diag, patch, gidx):
-        _lib.check(self.ctx.L.pmk_model_append(self.h, len(y), _d(x), _d(y), None if diag is None else _d(diag),
-                                               patch.ctypes.data_as(C.POINTER(C.c_int32)),
+        _lib.check(self.ctx.L.pmk_model_append(self.h, len(y), _d(x), _d(y), None if diag is None else _d(diag), _i32(patch),
                                                None if gidx is None else _i(gidx)), "pmk_model_append")
         self.n = self.n + np.bincount(patch, minlength=self.P).astype(np.int64)
-        self._loo_done = self._multi_solved = False
-        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+        self._rows_changed()
 
     def append(self, X_new_parts, y_new_parts, diag_parts=None):
         """pmk_model_append: X_new_parts[r] (m_r x D, m_r = 0 allowed) become the rows n_r .. n_r + m_r - 1 of patch r, with
         targets y_new_parts[r] and, on a model with set_diag addends, diag_parts[r] (None: zeros) -> info.  L, z and c of the
         resident factor are extended in place (no refit); loo() and the multi-output targets have to be set again."""
         self._need_appendable("append")
-        if getattr(self, "_from_tree", False):
+        if self._from_tree:
             raise _lib.PmkError("append: a model built by from_tree takes append_global")
         x, y, diag, patch, parts = append_items(X_new_parts, y_new_parts, diag_parts, self.n, self.D, self.capacity())
         if len(y):
@@ -567,18 +577,16 @@ class DeviceModel:
         return rows
 
     def _remove(self, patch, row):
-        _lib.check(self.ctx.L.pmk_model_remove(self.h, len(row), patch.ctypes.data_as(C.POINTER(C.c_int32)), _i(row)),
-                   "pmk_model_remove")
+        _lib.check(self.ctx.L.pmk_model_remove(self.h, len(row), _i32(patch), _i(row)), "pmk_model_remove")
         self.n = self.n - np.bincount(patch, minlength=self.P).astype(np.int64)
-        self._loo_done = self._multi_solved = False
-        self.R = 0                          # the multi-output targets are discarded: set_targets_multi again
+        self._rows_changed()
 
     def remove(self, rows_parts):
         """pmk_model_remove: rows_parts[r] is an integer array (empty allowed) of ZERO-based row indices of patch r as it
         stands before the call -> info.  L, z and c of the resident factor are reduced in place (no refit), the rows that
         stay keep their order; loo() and the multi-output targets have to be set again."""
         self._need_appendable("remove")
-        if getattr(self, "_from_tree", False):
+        if self._from_tree:
             raise _lib.PmkError("remove: a model built by from_tree takes remove_global")
         patch, row, parts = remove_items(rows_parts, self.n)
         if len(row):
@@ -618,23 +626,42 @@ class DeviceModel:
 class DeviceQuery:
     """pmk_query: a resident batch of query points and its (query, region) work items"""
 
+    # The mirror of the library's query state (include/pmk.h): what a fetch has to allocate, and what is refused
+    # before any device call.  These are the values of a query just created from points; every birth path (the
+    # constructor, from_items, a test's object.__new__) sets only what differs, and only the calls named here change them.
+    Xq = None               # the host copy of the points; None for a device array and after from_items
+    has_diag = False        # set_diag / set_diag_device addends of k(xq, xq) are set
+    total = 0               # the items of the plan: plan, predict_sharded, predict_allgather; from_items: its n
+    first_owned = 0         # plan: the items of this rank's own leaves are [first_owned, first_owned + num_owned)
+    num_owned = 0
+    R_items = 0             # the columns of the last items_multi / _multi_fitted / _loo_multi; 0 after a new plan
+    variance = False        # ... and whether they ran with the variance
+    grad_items = False      # items_grad ran on these items
+    vgrad_items = False     # items_vgrad ran on these items
+    block_F = 0             # the groups of the last items_block
+    block_variance = False  # ... and whether it ran with the variance
+
+    def _items_replaced(self, R, variance):
+        """plan (R = 0), items_multi, items_multi_fitted, items_loo_multi: the multi-output items are those of R columns,
+        with or without the variance, and the gradients of the earlier ones are gone, as in the library"""
+        self.variance, self.R_items = bool(variance), int(R)
+        self.grad_items = self.vgrad_items = False
+
     def __init__(self, model, Xq):
         self.model = model
         if isinstance(Xq, np.ndarray) or not hasattr(Xq, "__cuda_array_interface__"):
             self.Xq = as_points(Xq)
             ptr = _d(self.Xq)
+            self.Nq = self.Xq.shape[0]
         else:                                   # a device array (torch tensor): no host copy
             xa = GlobalArray(Xq, "Xq").points(model.D)
-            self.Xq, self._keep = None, Xq
+            self._keep = Xq
             ptr = C.cast(C.c_void_p(xa.ptr), _dp)
             self.Nq = xa.shape[0]
-        if self.Xq is not None:
-            self.Nq = self.Xq.shape[0]
         h = C.c_void_p()
         _lib.check(model.ctx.L.pmk_query_create(model.h, self.Nq, ptr, C.byref(h)), "pmk_query_create")
         self.h = h
         self.L = model.ctx.L
-        self.has_diag = False
 
     def set_diag(self, diag):
         """pmk_query_set_diag: per-query addend of k(xq, xq) in the predictive variance (None clears it)"""
@@ -664,11 +691,11 @@ class DeviceQuery:
         """pmk_query_create_items: n explicit (point, region) items received from other ranks; xq_ptr / region_ptr
         are raw host or device addresses (float64 n x D point-major, int32 n)"""
         self = cls.__new__(cls)
-        self.model, self.Xq, self.Nq, self.L, self.has_diag = model, None, int(n), model.ctx.L, False
+        self.model, self.Nq, self.L = model, int(n), model.ctx.L
         h = C.c_void_p()
         _lib.check(self.L.pmk_query_create_items(model.h, int(n), xq_ptr, region_ptr, C.byref(h)), "pmk_query_create_items")
         self.h = h
-        self.total, self.first_owned, self.num_owned = int(n), 0, int(n)
+        self.total = self.num_owned = int(n)
         return self
 
     def __del__(self):
@@ -690,8 +717,7 @@ class DeviceQuery:
         t, f, o = C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pmk_query_counts(self.h, C.byref(t), C.byref(f), C.byref(o)))
         self.total, self.first_owned, self.num_owned = t.value, f.value, o.value
-        self.R_items = 0                    # a new plan discards the items, as in the library
-        self.grad_items = self.vgrad_items = False
+        self._items_replaced(0, self.variance)      # a new plan discards the items; the variance flag stays as it was
         return self.total
 
     def region_offsets(self, P_global):
@@ -703,23 +729,26 @@ class DeviceQuery:
         d = theta.desc()
         _lib.check(self.L.pmk_query_items(self.h, C.byref(d)), "pmk_query_items")
 
+    def _range(self, q0, q1):
+        """the queries [q0, q1) of a mix call; q1=None: to the last"""
+        return int(q0), int(self.Nq if q1 is None else q1)
+
     def items_fitted(self):
         """pmk_query_items_fitted: stage 2 with the model's own kernels (region r with the theta it was fitted with)"""
-        if not getattr(self.model, "_has_kernels", False):
-            raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+        _need_kernels(self.model)
         _lib.check(self.L.pmk_query_items_fitted(self.h), "pmk_query_items_fitted")
 
     def _blend_loo_model(self, who):
         """the model, if the blended leave-one-out can run on it with this query (the states the library refuses too)"""
         m = self.model
-        if not getattr(m, "_from_tree", False):
+        if not m._from_tree:
             raise _lib.PmkError("%s: the model was built from lists of patches, not by from_tree" % who)
         if self.Nq != m.N:
             raise _lib.PmkError("%s: the query has %d points, the model %d: query j must be training point j"
                                 % (who, self.Nq, m.N))
-        if not getattr(m, "_all_leaves", False):
+        if not m._all_leaves:
             raise _lib.PmkError("%s: the model holds a shard of the leaves; the blended leave-one-out needs all" % who)
-        if not getattr(m, "_has_kernels", False):
+        if not m._has_kernels:
             raise _lib.PmkError("the model holds no kernels: fit it first")
         return m
 
@@ -747,30 +776,27 @@ class DeviceQuery:
         nm, no = C.c_int64(), C.c_int64()
         _lib.check(self.L.pmk_query_items_loo_multi(self.h, int(bool(noisy)), int(bool(variance)), C.byref(nm), C.byref(no)),
                    "pmk_query_items_loo_multi")
-        self.variance, self.R_items = bool(variance), int(m.R)
-        self.grad_items = self.vgrad_items = False
+        self._items_replaced(m.R, variance)
         return nm.value, no.value
 
     def item_values_multi(self):
         """pmk_query_get_items_multi -> (U [total, R], v [total] or None after a mean-only run): the per-item results of
         items_multi, items_multi_fitted or items_loo_multi in the item order of debug()"""
-        R = getattr(self, "R_items", 0)         # the R of the items run: the library writes that many columns
+        R = self.R_items                        # the R of the items run: the library writes that many columns
         if R < 1:
             raise _lib.PmkError("item_values_multi: no items_multi, items_multi_fitted or items_loo_multi has run")
         T = max(int(self.total), 1)
         U = np.empty((T, R))
-        v = np.empty(T) if getattr(self, "variance", False) else None
+        v = np.empty(T) if self.variance else None
         _lib.check(self.L.pmk_query_get_items_multi(self.h, _d(U), R, None if v is None else _d(v)),
                    "pmk_query_get_items_multi")
         return U[:self.total], (None if v is None else v[:self.total])
 
     def items_multi_fitted(self, variance=True):
         """pmk_query_items_multi_fitted: items_multi with the model's own kernels"""
-        if not getattr(self.model, "_has_kernels", False):
-            raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+        _need_kernels(self.model)
         _lib.check(self.L.pmk_query_items_multi_fitted(self.h, int(bool(variance))), "pmk_query_items_multi_fitted")
-        self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
-        self.grad_items = self.vgrad_items = False
+        self._items_replaced(self.model.R, variance)
 
     def item_buffers(self):
         u, v = C.c_void_p(), C.c_void_p()
@@ -800,7 +826,7 @@ class DeviceQuery:
 
     def mix(self, weight_theta, q0=0, q1=None):
         d = weight_theta.desc()
-        _lib.check(self.L.pmk_query_mix(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)), "pmk_query_mix")
+        _lib.check(self.L.pmk_query_mix(self.h, C.byref(d), *self._range(q0, q1)), "pmk_query_mix")
 
     def fetch(self):
         Yq, Vq = np.empty(self.Nq), np.empty(self.Nq)
@@ -814,6 +840,16 @@ class DeviceQuery:
             raise ValueError("%s must be a device array (__cuda_array_interface__); fetch() returns host arrays" % what)
         return ga
 
+    @classmethod
+    def _device_out_c(cls, a, what, shape):
+        """a C-contiguous device array of exactly `shape` (its last extent is Nq: nothing to check on an empty batch)"""
+        ga = cls._device_out(a, what)
+        strides = tuple(int(np.prod(shape[k + 1:], dtype=np.int64)) for k in range(len(shape)))
+        if ga.shape != shape or (shape[-1] > 0 and ga.strides != strides):
+            raise ValueError("%s must be a C-contiguous device array of shape (%s), not %s"
+                             % (what, ", ".join("%d" % v for v in shape), ga.shape))
+        return ga
+
     def fetch_into(self, Yq, Vq=None):
         """pmk_query_fetch_dev: the mixed results into device arrays of Nq float64 (torch tensors): device-to-device on
         the context's stream, no host synchronisation"""
@@ -824,12 +860,12 @@ class DeviceQuery:
     def fetch_multi_into(self, Yq, Vq=None):
         """pmk_query_fetch_multi_dev: Yq is a device array (Nq, R) in column-major order (its column stride is the leading
         dimension); Vq (Nq) only if the items ran with the variance"""
-        R = getattr(self.model, "R", 0)
+        R = self.model.R
         ya = self._device_out(Yq, "Yq")
         if len(ya.shape) != 2 or ya.shape[1] != R:
             raise ValueError("Yq must have shape (%d, %d), not %s" % (self.Nq, R, ya.shape))
         _, ld = ya.columns(self.Nq)
-        if Vq is not None and not getattr(self, "variance", False):
+        if Vq is not None and not self.variance:
             raise ValueError("Vq was not computed: the items ran mean-only (variance=False)")
         va = None if Vq is None else self._device_out(Vq, "Vq").vector(self.Nq)
         _lib.check(self.L.pmk_query_fetch_multi_dev(self.h, ya.ptr, ld, None if va is None else va.ptr),
@@ -838,13 +874,11 @@ class DeviceQuery:
     def items_multi(self, theta, variance=True):
         d = theta.desc()
         _lib.check(self.L.pmk_query_items_multi(self.h, C.byref(d), int(bool(variance))), "pmk_query_items_multi")
-        self.variance, self.R_items = bool(variance), int(getattr(self.model, "R", 0))
-        self.grad_items = self.vgrad_items = False
+        self._items_replaced(self.model.R, variance)
 
     def mix_multi(self, weight_theta, q0=0, q1=None):
         d = weight_theta.desc()
-        _lib.check(self.L.pmk_query_mix_multi(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
-                   "pmk_query_mix_multi")
+        _lib.check(self.L.pmk_query_mix_multi(self.h, C.byref(d), *self._range(q0, q1)), "pmk_query_mix_multi")
 
     def fetch_multi(self, R):
         """(Yq [Nq, R], Vq or None)"""
@@ -859,25 +893,18 @@ class DeviceQuery:
         """pmk_query_items_grad: the gradient of every item mean of the last items_multi / items_multi_fitted on this plan,
         with `theta` for every patch or (None) the model's own kernels.  Closure-carrying kernels raise TypeError and
         Brownian-bridge kernels ValueError before any device call."""
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            d = _grad_kernel(theta, "items_grad")
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _grad_kernel, "items_grad")
         _lib.check(self.L.pmk_query_items_grad(self.h, ptr), "pmk_query_items_grad")
         self.grad_items = True
 
     def mix_grad(self, weight_theta, q0=0, q1=None):
         """pmk_query_mix_grad: the gradient of the blend of mix_multi for queries [q0, q1), the item list held fixed"""
         d = _grad_kernel(weight_theta, "mix_grad")
-        _lib.check(self.L.pmk_query_mix_grad(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
-                   "pmk_query_mix_grad")
+        _lib.check(self.L.pmk_query_mix_grad(self.h, C.byref(d), *self._range(q0, q1)), "pmk_query_mix_grad")
 
     def fetch_grad(self):
         """dYq [Nq, R, D]: dYq[j, c, d] = dY_c/dx_d at query j"""
-        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
+        R, D = int(self.R_items), int(self.model.D)
         if R < 1:
             raise _lib.PmkError("fetch_grad: no items_multi or items_multi_fitted has run")
         buf = np.empty((R, D, max(self.Nq, 1)))                 # dYq[j + lddy (d + D c)]
@@ -887,22 +914,19 @@ class DeviceQuery:
     def fetch_grad_into(self, dYq):
         """pmk_query_fetch_grad_dev: dYq is a device array of shape (R, D, Nq), C-contiguous (element [c, d, j] is
         dY_c/dx_d at query j): device-to-device on the context's stream, no host synchronisation"""
-        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
-        ga = self._device_out(dYq, "dYq")
-        if ga.shape != (R, D, self.Nq) or (self.Nq > 0 and ga.strides != (D * self.Nq, self.Nq, 1)):
-            raise ValueError("dYq must be a C-contiguous device array of shape (%d, %d, %d), not %s" % (R, D, self.Nq, ga.shape))
+        ga = self._device_out_c(dYq, "dYq", (int(self.R_items), int(self.model.D), self.Nq))
         _lib.check(self.L.pmk_query_fetch_grad_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_grad_dev")
 
     def item_grads(self):
         """pmk_query_get_items_grad -> (G [total, R, D], plane [total]) in the item order of debug(): G[i, c, d] is the
         gradient of item i's mean of column c; plane[i] is the pre-order hyperplane (row of fetchhyperplanes' arrays) a
         neighbour item was accepted at, -1 for a home item.  G is None before items_grad."""
-        R, D = int(getattr(self, "R_items", 0)), int(self.model.D)
+        R, D = int(self.R_items), int(self.model.D)
         T = max(int(self.total), 1)
         plane = np.empty(T, dtype=np.int32)
-        G = np.empty((T, R, D)) if getattr(self, "grad_items", False) and R >= 1 else None
-        _lib.check(self.L.pmk_query_get_items_grad(self.h, None if G is None else _d(G), R * D,
-                                                   plane.ctypes.data_as(C.POINTER(C.c_int32))), "pmk_query_get_items_grad")
+        G = np.empty((T, R, D)) if self.grad_items and R >= 1 else None
+        _lib.check(self.L.pmk_query_get_items_grad(self.h, None if G is None else _d(G), R * D, _i32(plane)),
+                   "pmk_query_get_items_grad")
         return (None if G is None else G[:self.total]), plane[:self.total]
 
     # ---- gradient of the blended variance (pmk_vgrad.hip)
@@ -911,13 +935,7 @@ class DeviceQuery:
         plan, which must have run with the variance; `theta` for every patch or (None) the model's own kernels.  A query
         with set_diag addends is refused.  Closure-carrying kernels raise TypeError and Brownian-bridge kernels ValueError
         before any device call."""
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            d = _grad_kernel(theta, "items_vgrad")
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _grad_kernel, "items_vgrad")
         _lib.check(self.L.pmk_query_items_vgrad(self.h, ptr), "pmk_query_items_vgrad")
         self.vgrad_items = True
 
@@ -925,8 +943,7 @@ class DeviceQuery:
         """pmk_query_mix_vgrad: the gradient of the blended variance of mix_multi for queries [q0, q1), the item list held
         fixed"""
         d = _grad_kernel(weight_theta, "mix_vgrad")
-        _lib.check(self.L.pmk_query_mix_vgrad(self.h, C.byref(d), int(q0), int(self.Nq if q1 is None else q1)),
-                   "pmk_query_mix_vgrad")
+        _lib.check(self.L.pmk_query_mix_vgrad(self.h, C.byref(d), *self._range(q0, q1)), "pmk_query_mix_vgrad")
 
     def fetch_vgrad(self):
         """dVq [Nq, D]: dVq[j, d] = dVq/dx_d at query j"""
@@ -938,16 +955,13 @@ class DeviceQuery:
     def fetch_vgrad_into(self, dVq):
         """pmk_query_fetch_vgrad_dev: dVq is a device array of shape (D, Nq), C-contiguous (element [d, j] is dVq/dx_d at
         query j): device-to-device on the context's stream, no host synchronisation"""
-        D = int(self.model.D)
-        ga = self._device_out(dVq, "dVq")
-        if ga.shape != (D, self.Nq) or (self.Nq > 0 and ga.strides != (self.Nq, 1)):
-            raise ValueError("dVq must be a C-contiguous device array of shape (%d, %d), not %s" % (D, self.Nq, ga.shape))
+        ga = self._device_out_c(dVq, "dVq", (int(self.model.D), self.Nq))
         _lib.check(self.L.pmk_query_fetch_vgrad_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_vgrad_dev")
 
     def item_vgrads(self):
         """pmk_query_get_items_vgrad -> GV [total, D] in the item order of debug(): GV[i, d] is the gradient of item i's
         variance"""
-        if not getattr(self, "vgrad_items", False):
+        if not self.vgrad_items:
             raise _lib.PmkError("item_vgrads: items_vgrad has not run on this plan")
         D = int(self.model.D)
         GV = np.empty((max(int(self.total), 1), D))
@@ -959,14 +973,7 @@ class DeviceQuery:
         """pmk_query_items_cov: the posterior covariance block of every region over its items of this plan, with `theta`
         for every patch or (None) the model's own kernels.  Single-output path: no trend, no targets needed.  Serves a
         query made by from_items too.  Closure-carrying kernels raise TypeError before any device call."""
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            _refuse_closure_kernel(theta, "items_cov")
-            d = theta.desc()
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _closure_free_kernel, "items_cov")
         _lib.check(self.L.pmk_query_items_cov(self.h, ptr), "pmk_query_items_cov")
 
     def items_cov_multi(self, theta=None):
@@ -975,20 +982,12 @@ class DeviceQuery:
         is the item variance of items_multi); without one they are those of items_cov bit for bit.  `theta` is the kernel
         given to the items call, or (None) the model's own.  mix_cov, fetch_cov and item_covs serve the results.
         Closure-carrying kernels raise TypeError before any device call."""
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            _refuse_closure_kernel(theta, "items_cov_multi")
-            d = theta.desc()
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _closure_free_kernel, "items_cov_multi")
         _lib.check(self.L.pmk_query_items_cov_multi(self.h, ptr), "pmk_query_items_cov_multi")
 
     def mix_cov(self, weight_theta):
         """pmk_query_mix_cov: the joint covariance of the whole batch under the blend of mix()"""
-        _refuse_closure_kernel(weight_theta, "mix_cov")
-        d = weight_theta.desc()
+        d = _closure_free_kernel(weight_theta, "mix_cov")
         _lib.check(self.L.pmk_query_mix_cov(self.h, C.byref(d)), "pmk_query_mix_cov")
 
     def fetch_cov(self):
@@ -1001,9 +1000,7 @@ class DeviceQuery:
     def fetch_cov_into(self, Cov):
         """pmk_query_fetch_cov_dev: Cov is a contiguous device array of shape (Nq, Nq) of float64 (a torch tensor):
         device-to-device on the context's stream, no host synchronisation"""
-        ga = self._device_out(Cov, "Cov")
-        if ga.shape != (self.Nq, self.Nq) or (self.Nq > 0 and ga.strides != (self.Nq, 1)):
-            raise ValueError("Cov must be a C-contiguous device array of shape (%d, %d), not %s" % (self.Nq, self.Nq, ga.shape))
+        ga = self._device_out_c(Cov, "Cov", (self.Nq, self.Nq))
         _lib.check(self.L.pmk_query_fetch_cov_dev(self.h, ga.ptr, max(self.Nq, 1)), "pmk_query_fetch_cov_dev")
 
     def item_covs(self, region):
@@ -1014,8 +1011,7 @@ class DeviceQuery:
         n = max(m.value, 1)
         idx = np.empty(n, dtype=np.int32)
         S = np.empty((n, n))
-        _lib.check(self.L.pmk_query_get_items_cov(self.h, int(region), None, idx.ctypes.data_as(C.POINTER(C.c_int32)), _d(S), n),
-                   "pmk_query_get_items_cov")
+        _lib.check(self.L.pmk_query_get_items_cov(self.h, int(region), None, _i32(idx), _d(S), n), "pmk_query_get_items_cov")
         return idx[:m.value], S[:m.value, :m.value]
 
     # ---- block kriging: weighted sums over groups of queries (pmk_block.hip)
@@ -1032,23 +1028,16 @@ class DeviceQuery:
             raise ValueError("one group and one coefficient per query point (%d), not %d and %d" % (self.Nq, len(g), len(c)))
         if F is None:
             F = int(g[-1]) + 1 if len(g) else 0
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            _refuse_closure_kernel(theta, "items_block")
-            d = theta.desc()
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _closure_free_kernel, "items_block")
         w = weight_theta.desc()
-        _lib.check(self.L.pmk_query_items_block(self.h, ptr, C.byref(w), int(F), g.ctypes.data_as(C.POINTER(C.c_int32)), _d(c),
-                                                int(bool(variance))), "pmk_query_items_block")
+        _lib.check(self.L.pmk_query_items_block(self.h, ptr, C.byref(w), int(F), _i32(g), _d(c), int(bool(variance))),
+                   "pmk_query_items_block")
         self.block_F, self.block_variance = int(F), bool(variance)
 
     def fetch_block(self):
         """(Yb [F, R], Vb [F] or None after variance=False)"""
-        F, R = getattr(self, "block_F", 0), int(getattr(self, "R_items", 0))
-        Vb = np.empty(F) if getattr(self, "block_variance", False) else None
+        F, R = self.block_F, int(self.R_items)
+        Vb = np.empty(F) if self.block_variance else None
         buf = np.empty((max(F, 1), max(R, 1)), order="F")
         _lib.check(self.L.pmk_query_fetch_block(self.h, _d(buf), max(F, 1), None if Vb is None else _d(Vb)),
                    "pmk_query_fetch_block")
@@ -1057,12 +1046,12 @@ class DeviceQuery:
     def fetch_block_into(self, Yb, Vb=None):
         """pmk_query_fetch_block_dev: Yb is a device array (F, R) in column-major order (its column stride is the leading
         dimension); Vb (F) only if items_block ran with the variance"""
-        F, R = getattr(self, "block_F", 0), int(getattr(self, "R_items", 0))
+        F, R = self.block_F, int(self.R_items)
         ya = self._device_out(Yb, "Yb")
         if len(ya.shape) != 2 or ya.shape != (F, R):
             raise ValueError("Yb must have shape (%d, %d), not %s" % (F, R, ya.shape))
         _, ld = ya.columns(F)
-        if Vb is not None and not getattr(self, "block_variance", False):
+        if Vb is not None and not self.block_variance:
             raise ValueError("Vb was not computed: items_block ran mean-only (variance=False)")
         va = None if Vb is None else self._device_out(Vb, "Vb").vector(F)
         _lib.check(self.L.pmk_query_fetch_block_dev(self.h, ya.ptr, ld, None if va is None else va.ptr),
@@ -1078,9 +1067,8 @@ class DeviceQuery:
         i32 = lambda: np.empty(k, dtype=np.int32)
         out = dict(region=i32(), group=i32(), first=np.empty(k, dtype=np.int64), count=i32(), kappa=np.empty(k),
                    vnorm2=np.empty(k), znorm2=np.empty(k), sw2=np.empty(k))
-        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.pmk_query_get_items_block(self.h, None, p32(out["region"]), p32(out["group"]), _i(out["first"]),
-                                                    p32(out["count"]), _d(out["kappa"]), _d(out["vnorm2"]),
+        _lib.check(self.L.pmk_query_get_items_block(self.h, None, _i32(out["region"]), _i32(out["group"]), _i(out["first"]),
+                                                    _i32(out["count"]), _d(out["kappa"]), _d(out["vnorm2"]),
                                                     _d(out["znorm2"]), _d(out["sw2"])), "pmk_query_get_items_block")
         return {key: v[:n.value] for key, v in out.items()}
 
@@ -1088,14 +1076,7 @@ class DeviceQuery:
     def items_cov_blocks(self, theta=None, multi=False):
         """pmk_query_items_cov_blocks: the region blocks of items_cov (multi=False) or items_cov_multi (multi=True) for a
         batch of any size: what factor_cov and draw need.  mix_cov refuses such blocks on more than 16384 queries."""
-        if theta is None:
-            if not getattr(self.model, "_has_kernels", False):
-                raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
-            ptr = None
-        else:
-            _refuse_closure_kernel(theta, "items_cov_blocks")
-            d = theta.desc()
-            ptr = C.byref(d)
+        ptr, _keep = _theta_arg(self.model, theta, _closure_free_kernel, "items_cov_blocks")
         _lib.check(self.L.pmk_query_items_cov_blocks(self.h, ptr, 1 if multi else 0), "pmk_query_items_cov_blocks")
 
     def factor_cov(self, rel=None):
@@ -1115,7 +1096,7 @@ class DeviceQuery:
         patch is failed or its trend flagged; the absolute jitter that was added.  Blocks."""
         P = int(self.model.P)
         finfo, jitter = np.zeros(P, dtype=np.int32), np.zeros(P)
-        rc = self.L.pmk_query_factor_info(self.h, finfo.ctypes.data_as(C.POINTER(C.c_int32)), _d(jitter))
+        rc = self.L.pmk_query_factor_info(self.h, _i32(finfo), _d(jitter))
         if rc < 0:
             _lib.check(rc, "pmk_query_factor_info")
         return finfo, jitter
@@ -1139,7 +1120,7 @@ class DeviceQuery:
         _refuse_closure_kernel(weight_theta, "draw")
         za = GlobalArray(z, "z")
         if len(za.shape) != 2 or za.shape[1] != int(self.total):
-            raise ValueError("z must have shape (n_draws, %d), not %s" % (self.total, za.shape))
+            raise _z_shape_error("(n_draws, %d)" % self.total, za.shape)
         n = za.shape[0]
         if za.shape[1] > 1 and za.strides[1] != 1:
             raise ValueError("z must have contiguous rows")
@@ -1170,12 +1151,35 @@ class DeviceQuery:
                     item_v=v[:n])
 
 
+def _need_kernels(model):
+    """the calls that run on the model's own kernels; the model of a query may be a test's plain stand-in"""
+    if not getattr(model, "_has_kernels", False):
+        raise _lib.PmkError("the model holds no kernels: fit it, or set_kernels on a model built from factors")
+
+
+def _theta_arg(model, theta, check, who):
+    """the pmk_kernel_desc * argument of a query call that takes `theta` for every patch or (None) the model's own kernels
+    -> (pointer, descriptor).  check(theta, who) -> descriptor refuses what the call cannot take (_grad_kernel,
+    _closure_free_kernel); the descriptor has to live until the library call returns."""
+    if theta is None:
+        _need_kernels(model)
+        return None, None
+    d = check(theta, who)
+    return C.byref(d), d
+
+
+def _closure_free_kernel(theta, who):
+    """the descriptor of a kernel the covariance, block and draw calls accept: closure-carrying kernels are refused
+    (TypeError) before any device call"""
+    _refuse_closure_kernel(theta, who)
+    return theta.desc()
+
+
 def _grad_kernel(theta, who):
     """the descriptor of a kernel the gradient calls accept, checked before any device call: closure-carrying kernels are
     refused with the TypeError of the trend, the Brownian-bridge families (not differentiable on the diagonal) with a
     ValueError"""
-    _refuse_closure_kernel(theta, who)
-    d = theta.desc()
+    d = _closure_free_kernel(theta, who)
     if d.family >= 10:                          # PMK_BB10 .. PMK_BB2EPS
         raise ValueError("%s: %s is a Brownian-bridge kernel, which is not differentiable on the diagonal: no gradient"
                          % (who, type(theta).__name__))
@@ -1478,14 +1482,20 @@ def appendmixtureGP_(eta, X_new_parts, y_new_parts):
     model = _fitted_model(eta, "appendmixtureGP_")
     if getattr(model, "theta", None) is not None:
         _refuse_closure_kernel(model.theta, "appendmixtureGP_")
+    return _store_changed_rows(eta, model, model.append_global, model.append, X_new_parts, y_new_parts)
+
+
+def _store_changed_rows(eta, model, on_tree, on_lists, *args):
+    """the common end of appendmixtureGP_ and removemixtureGP_: the model's *_global call on an eta built by from_tree, its
+    list call otherwise, then c_set, L_set, U_set and X_parts follow the resident model -> eta"""
     if getattr(eta, "_from_tree", False):
-        model.append_global(X_new_parts, y_new_parts)
+        on_tree(*args)
         info = model.info()
     else:
-        info = model.append(X_new_parts, y_new_parts)
+        info = on_lists(*args)
         eta.X_parts = model.X
     _store_fit(eta, model, model.weights(), eta.sigma2_set)
-    eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the append: fit those again
+    eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the rows: fit those again
     _raise_if_failed(info)
     return eta
 
@@ -1508,16 +1518,7 @@ def removemixtureGP_(eta, rows_parts):
     refitted; c_set, L_set, U_set and X_parts follow.  Raises PosDefException(patch, k) like fitmixtureGP_ when a new
     diagonal fails: that patch is then failed as after a failed fit until the next fit."""
     model = _fitted_model(eta, "removemixtureGP_")
-    if getattr(eta, "_from_tree", False):
-        model.remove_global(rows_parts)
-        info = model.info()
-    else:
-        info = model.remove(rows_parts)
-        eta.X_parts = model.X
-    _store_fit(eta, model, model.weights(), eta.sigma2_set)
-    eta.C_set = eta.beta_set = None     # the multi-output and trend state went with the rows: fit those again
-    _raise_if_failed(info)
-    return eta
+    return _store_changed_rows(eta, model, model.remove_global, model.remove, rows_parts)
 
 
 class MixtureGPDebugType:
@@ -1527,6 +1528,14 @@ class MixtureGPDebugType:
         self.w_tilde_set, self.u_set, self.v_set = [], [], []
         self.region_inds_set, self.p_region_ind_set = [], []
         self.hps_keep_flags_set, self.zs_set, self.ts_set = [], [], []
+
+
+def _query_points(Xq):
+    """query points as an (Nq, D) array; one point may come as a vector"""
+    Xq = np.asarray(Xq, dtype=np.float64)
+    if Xq.ndim == 1:
+        Xq = Xq[None, :]
+    return Xq
 
 
 def querymixtureGP_(Yq, Vq, Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta, debug_vars,
@@ -1576,9 +1585,7 @@ def querymixtureGP_(Yq, Vq, Xq, eta, root, levels, radius, delta, theta, sigma2,
 
 def querymixtureGP(Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta, debug_flag=False):
     """querymixtureGP(Xq or xq, η, ...) -> Yq, Vq, debug_vars   (mixtureGP.jl:120-157)"""
-    Xq = np.asarray(Xq, dtype=np.float64)
-    if Xq.ndim == 1:
-        Xq = Xq[None, :]
+    Xq = _query_points(Xq)
     Yq, Vq = np.empty(0), np.empty(0)
     dbg = MixtureGPDebugType(1.0)
     querymixtureGP_(Yq, Vq, Xq, eta, root, levels, radius, delta, theta, sigma2, weight_theta, dbg, debug_flag)
@@ -1602,28 +1609,39 @@ def queryinner(xq, X, theta, c, L):
     return float(mu[0]), float(var[0])
 
 
+def _fit_columns(eta, Y_parts, theta, sigma2, who, trend=None):
+    """fitmixtureGP_ on column 0, then the R columns as the model's multi-output targets -> the model.  On an eta built
+    by from_tree (which takes no closure-carrying kernel) Y_parts is the GLOBAL (N, R) column-major array, whose first
+    column is N contiguous values; otherwise one vector or n_r x R matrix per patch.  trend: R + q <= MAX_OUTPUTS is
+    checked before the fit (None: q = 0, and the targets' own check has bounded R)."""
+    if getattr(eta, "_from_tree", False):
+        _refuse_closure_kernel(theta, who)
+        model = eta._tree_model
+        ya = GlobalArray(Y_parts, "Y")
+        R, _ = ya.columns(model.N)
+        if trend is not None:
+            trend_columns(trend, model.D, R)
+        col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
+        fitmixtureGP_(eta, col0, theta, sigma2)
+        model.set_targets_multi_global(Y_parts)
+        return model
+    Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
+    if trend is not None:
+        trend_columns(trend, eta.X_parts[0].shape[1], Ys[0].shape[1])
+    fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
+    model = eta._model
+    model.set_targets_multi(Ys)
+    return model
+
+
 def fitmixtureGP_multi_(eta, Y_parts, theta, sigma2):
     """fitmixtureGP! (mixtureGP.jl:70-118) with R target columns per patch that share one factor: the fit runs once on
     column 0 (c_set, L_set as fitmixtureGP_ leaves them), then every column is solved from the resident factor
     (c = U \\ y of mixtureGP.jl:106 for R right-hand sides).  Stores eta.C_set (a list of n_r x R)."""
     eta.beta_set = None             # the coefficients of an earlier fitmixtureGP_trend_ do not belong to this fit
+    model = _fit_columns(eta, Y_parts, theta, sigma2, "fitmixtureGP_multi_")
     if getattr(eta, "_from_tree", False):
-        # Y_parts is the GLOBAL (N, R) column-major array; its first column is N contiguous values
-        _refuse_closure_kernel(theta, "fitmixtureGP_multi_")
-        model = eta._tree_model
-        ya = GlobalArray(Y_parts, "Y")
-        ya.columns(model.N)
-        col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
-        fitmixtureGP_(eta, col0, theta, sigma2)
-        model.set_targets_multi_global(Y_parts)
         model.set_trend(None)           # the resident model may carry the trend of an earlier fitmixtureGP_trend_
-        model.solve_multi()
-        eta.C_set = model.weights_multi()
-        return eta
-    Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
-    fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
-    model = eta._model
-    model.set_targets_multi(Ys)
     model.solve_multi()
     eta.C_set = model.weights_multi()
     return eta
@@ -1638,20 +1656,7 @@ def fitmixtureGP_trend_(eta, Y_parts, theta, sigma2, trend="constant"):
     GLS one) and loomixtureGP_multi serve unchanged.  Raises TrendRankException for a flagged patch."""
     trend_degree(trend)
     _refuse_closure_kernel(theta, "fitmixtureGP_trend_")     # a warp-feature model has more coordinates than positions
-    if getattr(eta, "_from_tree", False):
-        model = eta._tree_model
-        ya = GlobalArray(Y_parts, "Y")
-        R, _ = ya.columns(model.N)
-        trend_columns(trend, model.D, R)
-        col0 = Y_parts if len(ya.shape) == 1 else Y_parts[:, 0]
-        fitmixtureGP_(eta, col0, theta, sigma2)
-        model.set_targets_multi_global(Y_parts)
-    else:
-        Ys = multi_targets(Y_parts, [x.shape[0] for x in eta.X_parts])
-        trend_columns(trend, eta.X_parts[0].shape[1], Ys[0].shape[1])
-        fitmixtureGP_(eta, [y[:, 0].copy() for y in Ys], theta, sigma2)
-        model = eta._model
-        model.set_targets_multi(Ys)
+    model = _fit_columns(eta, Y_parts, theta, sigma2, "fitmixtureGP_trend_", trend)
     model.set_trend(trend)
     model.solve_multi()
     flags = model.trend_info()
@@ -1668,10 +1673,7 @@ def querymixtureGP_multi(Xq, eta, root, levels, radius, delta, theta, sigma2, we
     variance=False runs no triangular solve: the means need only kq . C (queryinner!, mixtureGP.jl:296-316)."""
     if eta._model is None or getattr(eta, "C_set", None) is None:
         raise _lib.PmkError("fitmixtureGP_multi_ must run before querymixtureGP_multi")
-    Xq = np.asarray(Xq, dtype=np.float64)
-    if Xq.ndim == 1:
-        Xq = Xq[None, :]
-    Xq = as_points(Xq)
+    Xq = as_points(_query_points(Xq))
     model = eta._model
     model.set_bsp(root, 0)
     q = DeviceQuery(model, kernel_points(theta, Xq))
@@ -1695,10 +1697,7 @@ def querymixtureGP_grad(Xq, eta, root, levels, radius, delta, theta, sigma2, wei
     _grad_kernel(weight_theta, "querymixtureGP_grad")
     if eta._model is None or getattr(eta, "C_set", None) is None:
         raise _lib.PmkError("fitmixtureGP_multi_ must run before querymixtureGP_grad")
-    Xq = np.asarray(Xq, dtype=np.float64)
-    if Xq.ndim == 1:
-        Xq = Xq[None, :]
-    Xq = as_points(Xq)
+    Xq = as_points(_query_points(Xq))
     model = eta._model
     model.set_bsp(root, 0)
     q = DeviceQuery(model, Xq)
@@ -1725,18 +1724,23 @@ def _fitted_model(eta, who):
     return eta._model
 
 
+def _log_evidence(logdet, quad, n):
+    """-1/2 y^T c - 1/2 log det (K + sigma2 I) - n/2 log(2 pi)"""
+    return -0.5 * quad - 0.5 * logdet - 0.5 * n * np.log(2.0 * np.pi)
+
+
 def logevidencemixtureGP(eta):
     """log marginal likelihood of every patch, -1/2 y^T c - 1/2 log det (K + sigma2 I) - n/2 log(2 pi)  -> array [P]"""
     model = _fitted_model(eta, "logevidencemixtureGP")
     logdet, quad = model.evidence()
-    return -0.5 * quad - 0.5 * logdet - 0.5 * model.n * np.log(2.0 * np.pi)
+    return _log_evidence(logdet, quad, model.n)
 
 
 def logevidencemixtureGP_multi(eta):
     """the same for the R columns of fitmixtureGP_multi_ -> array [P, R] (one log det per patch serves every column)"""
     model = _fitted_model(eta, "logevidencemixtureGP_multi")
     logdet, quad = model.evidence_multi()
-    return -0.5 * quad - 0.5 * logdet[:, None] - 0.5 * model.n[:, None] * np.log(2.0 * np.pi)
+    return _log_evidence(logdet[:, None], quad, model.n[:, None])
 
 
 def loomixtureGP(eta):
@@ -1778,9 +1782,7 @@ def fitmixtureGP_patches_(eta, y_parts, thetas, sigma2s):
 def _patches_query(Xq, eta, root, radius, delta, who):
     if getattr(eta, "_model", None) is None or not getattr(eta._model, "_has_kernels", False):
         raise _lib.PmkError("fitmixtureGP_patches_ (or fitmixtureGP_) must run before %s" % who)
-    Xq = np.asarray(Xq, dtype=np.float64)
-    if Xq.ndim == 1:
-        Xq = Xq[None, :]
+    Xq = _query_points(Xq)
     model = eta._model
     model.set_bsp(root, 0)
     q = DeviceQuery(model, as_points(Xq))
@@ -1798,18 +1800,34 @@ def querymixtureGP_patches(Xq, eta, root, levels, radius, delta, weight_theta, d
     return Yq, Vq, (q.debug() if debug_flag else None)
 
 
-def _cov_query(Xq, eta, root, radius, delta, weight_theta, who):
-    """the planned query of the covariance front ends, with the means, variances and region blocks computed on the
-    model's own kernels.  Closure-carrying kernels (the blending profile, or the theta of the fit) raise TypeError before
-    any device call, as in the gradient front ends: their addends and warp features are functions of x the batch's joint
-    covariance would have to carry."""
+def _refuse_closure_front_end(eta, weight_theta, who):
+    """closure-carrying kernels (the blending profile, then the theta of the fit) raise TypeError before any device call,
+    as in the gradient front ends: their addends and warp features are functions of x the batch's joint covariance would
+    have to carry"""
     _refuse_closure_kernel(weight_theta, who)
     theta = getattr(getattr(eta, "_model", None), "theta", None)
     if theta is not None:
         _refuse_closure_kernel(theta, who)
+
+
+def _fitted_query(Xq, eta, root, radius, delta, weight_theta, who, multi, variance=True, mix=True):
+    """the planned query of the covariance, draw and block front ends, closure-carrying kernels refused: the items on the
+    model's own kernels, of the single-output path or (multi) of the R resident columns, and (mix) their blend"""
+    _refuse_closure_front_end(eta, weight_theta, who)
     q = _patches_query(Xq, eta, root, radius, delta, who)
-    q.items_fitted()
-    q.mix(weight_theta)
+    if multi:
+        q.model._need(multi=True)
+        q.items_multi_fitted(variance)
+    else:
+        q.items_fitted()
+    if mix:
+        (q.mix_multi if multi else q.mix)(weight_theta)
+    return q
+
+
+def _cov_query(Xq, eta, root, radius, delta, weight_theta, who):
+    """_fitted_query with the region blocks and the joint covariance of the batch"""
+    q = _fitted_query(Xq, eta, root, radius, delta, weight_theta, who, False)
     q.items_cov()
     q.mix_cov(weight_theta)
     return q
@@ -1823,6 +1841,53 @@ def querymixtureGP_cov(Xq, eta, root, levels, radius, delta, weight_theta):
     q = _cov_query(Xq, eta, root, radius, delta, weight_theta, "querymixtureGP_cov")
     Yq, Vq = q.fetch()
     return Yq, Vq, q.fetch_cov()
+
+
+def _z_shape_error(want, got):
+    return ValueError("z must have shape %s, not %s" % (want, got))
+
+
+def _normals(z, shape, dev, generator):
+    """the standard normals of the draws as a float64 tensor of `shape` on `dev`: z if given, else from `generator`"""
+    import torch
+
+    if z is None:
+        return torch.randn(shape, dtype=torch.float64, device=dev, generator=generator)
+    z = torch.as_tensor(z, dtype=torch.float64, device=dev)
+    if tuple(z.shape) != shape:
+        raise _z_shape_error(shape, tuple(z.shape))
+    return z
+
+
+def _dense_draw(q, n_draws, R, generator, z, who, nan_patch):
+    """method="dense" of the sampling front ends, on a query whose joint covariance is mixed -> (L, z, jitter): the
+    covariance fetched into a device tensor, refused with `nan_patch` (what a patch behind a NaN suffers from) if it is
+    not finite, its Cholesky factor under the jitter ladder of samplemixtureGP, and the normals z [n_draws, Nq] or
+    (R columns) [n_draws, Nq, R]"""
+    import torch
+
+    dev = torch.device("cuda", q.model.ctx.device)
+    Nq = q.Nq
+    Cov = torch.empty((Nq, Nq), dtype=torch.float64, device=dev)
+    q.fetch_cov_into(Cov)
+    q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
+    if not bool(torch.isfinite(Cov).all()):
+        # a query that blends a patch whose factorisation failed is NaN in its row and column; the factorisation need
+        # not report a NaN through info, and the draws would be NaN with jitter == 0.0
+        raise np.linalg.LinAlgError("%s: the joint covariance holds NaN or Inf entries: a query of the batch blends a patch "
+                                    "%s" % (who, nan_patch))
+    scale = float(torch.trace(Cov)) / max(Nq, 1)
+    jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
+    while True:
+        L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
+        if int(info) == 0:
+            break
+        jitter = 2.0 ** -52 * scale if jitter == 0.0 else 10.0 * jitter
+        if not jitter <= 2.0 ** -26 * scale:
+            raise np.linalg.LinAlgError("%s: the joint covariance is not positive definite with a jitter of up to 2^-26 "
+                                        "trace / Nq" % who)
+    shape = (int(n_draws), Nq) if R is None else (int(n_draws), Nq, R)
+    return L, _normals(z, shape, dev, generator), jitter
 
 
 def _sample_blocks(q, multi, weight_theta, n_draws, generator, z, who):
@@ -1855,13 +1920,7 @@ def _sample_blocks(q, multi, weight_theta, n_draws, generator, z, who):
         q.factor_cov(rel)
     jitter = float(jit.max()) if P else 0.0
     n, total = int(n_draws), int(q.total)
-    shape = (n, total) if R is None else (n, total, R)
-    if z is None:
-        z = torch.randn(shape, dtype=torch.float64, device=dev, generator=generator)
-    else:
-        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
-        if tuple(z.shape) != shape:
-            raise ValueError("z must have shape %s, not %s" % (shape, tuple(z.shape)))
+    z = _normals(z, (n, total) if R is None else (n, total, R), dev, generator)
     torch.cuda.synchronize(dev)                 # torch wrote z on its own stream, the library reads on the context's
     if R is None:
         E = q.draw(weight_theta, z.contiguous())
@@ -1873,8 +1932,8 @@ def _sample_blocks(q, multi, weight_theta, n_draws, generator, z, who):
 
 def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None, method="dense"):
     """posterior draws of the latent blended field at Xq -> (draws [n_draws, Nq] as a torch device tensor, jitter).
-    The joint covariance of querymixtureGP_cov is fetched into a device tensor and factored with
-    torch.linalg.cholesky_ex; if that fails, jitter * I is added, starting at 2^-52 trace / Nq and multiplied by 10 up to
+    The joint covariance of querymixtureGP_cov is fetched into a device tensor and factored with torch's Cholesky
+    (_dense_draw); if that fails, jitter * I is added, starting at 2^-52 trace / Nq and multiplied by 10 up to
     2^-26 trace / Nq, after which LinAlgError is raised.  A batch that blends a patch whose factorisation failed has NaN
     in its covariance and raises LinAlgError before any factorisation.  The jitter that was used is returned (0.0: none).  z
     [n_draws, Nq]: the standard normals to use; otherwise they are drawn from `generator`.  draws = Yq + z L^T.
@@ -1888,62 +1947,24 @@ def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws,
 
     if method not in ("dense", "blocks"):
         raise ValueError("method must be \"dense\" or \"blocks\", not %r" % (method,))
+    who = "samplemixtureGP"
     if method == "blocks":
-        who = "samplemixtureGP"
-        _refuse_closure_kernel(weight_theta, who)
-        theta = getattr(getattr(eta, "_model", None), "theta", None)
-        if theta is not None:
-            _refuse_closure_kernel(theta, who)
-        q = _patches_query(Xq, eta, root, radius, delta, who)
-        q.items_fitted()
-        q.mix(weight_theta)
-        Yq = torch.empty(q.Nq, dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))
-        q.fetch_into(Yq)
+        q = _fitted_query(Xq, eta, root, radius, delta, weight_theta, who, False)
+    else:
+        q = _cov_query(Xq, eta, root, radius, delta, weight_theta, who)
+    Yq = torch.empty(q.Nq, dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))
+    q.fetch_into(Yq)
+    if method == "blocks":
         E, jitter = _sample_blocks(q, False, weight_theta, n_draws, generator, z, who)
         return Yq[None, :] + E, jitter
-    q = _cov_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP")
-    dev = torch.device("cuda", q.model.ctx.device)
-    Nq = q.Nq
-    Cov = torch.empty((Nq, Nq), dtype=torch.float64, device=dev)
-    Yq = torch.empty(Nq, dtype=torch.float64, device=dev)
-    q.fetch_into(Yq)
-    q.fetch_cov_into(Cov)
-    q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
-    if not bool(torch.isfinite(Cov).all()):
-        # a query that blends a patch whose factorisation failed is NaN in its row and column; cholesky_ex need not
-        # report a NaN through info, and the draws would be NaN with jitter == 0.0
-        raise np.linalg.LinAlgError("samplemixtureGP: the joint covariance holds NaN or Inf entries: a query of the batch "
-                                    "blends a patch whose factorisation failed (DeviceModel.info())")
-    scale =float(torch.trace(Cov)) / max(Nq, 1)
-    jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
-    while True:
-        L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
-        if int(info) == 0:
-            break
-        jitter = 2.0 ** -52 * scale if jitter == 0.0 else 10.0 * jitter
-        if not jitter <= 2.0 ** -26 * scale:
-            raise np.linalg.LinAlgError("samplemixtureGP: the joint covariance is not positive definite with a jitter "
-                                        "of up to 2^-26 trace / Nq")
-    if z is None:
-        z = torch.randn((int(n_draws), Nq), dtype=torch.float64, device=dev, generator=generator)
-    else:
-        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
-        if tuple(z.shape) != (int(n_draws), Nq):
-            raise ValueError("z must have shape (%d, %d), not %s" % (int(n_draws), Nq, tuple(z.shape)))
+    L, z, jitter = _dense_draw(q, n_draws, None, generator, z, who, "whose factorisation failed (DeviceModel.info())")
     return Yq[None, :] + z @ L.T, jitter
 
 
 def _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, who):
     """_cov_query on the multi-output path: the R blended means, the variances and the region blocks with the term of
     the model's trend, on what fitmixtureGP_multi_ / fitmixtureGP_trend_ left resident"""
-    _refuse_closure_kernel(weight_theta, who)
-    theta = getattr(getattr(eta, "_model", None), "theta", None)
-    if theta is not None:
-        _refuse_closure_kernel(theta, who)
-    q = _patches_query(Xq, eta, root, radius, delta, who)
-    q.model._need(multi=True)
-    q.items_multi_fitted(True)
-    q.mix_multi(weight_theta)
+    q = _fitted_query(Xq, eta, root, radius, delta, weight_theta, who, True)
     q.items_cov_multi()
     q.mix_cov(weight_theta)
     return q
@@ -1967,14 +1988,7 @@ def querymixtureGP_block(Xq, group, a, eta, root, levels, radius, delta, weight_
     per query.  A block average over g points is a = 1 / g, an integral takes quadrature weights, a contrast mixes signs.
     Vb is a^T Cov a of querymixtureGP_cov_multi without the Nq x Nq matrix and without its limit of 16384 queries.
     Closure-carrying kernels raise TypeError before any device call."""
-    who = "querymixtureGP_block"
-    _refuse_closure_kernel(weight_theta, who)
-    theta = getattr(getattr(eta, "_model", None), "theta", None)
-    if theta is not None:
-        _refuse_closure_kernel(theta, who)
-    q = _patches_query(Xq, eta, root, radius, delta, who)
-    q.model._need(multi=True)
-    q.items_multi_fitted(False)
+    q = _fitted_query(Xq, eta, root, radius, delta, weight_theta, "querymixtureGP_block", True, variance=False, mix=False)
     q.items_block(group, a, weight_theta, variance=variance)
     return q.fetch_block()
 
@@ -1982,7 +1996,7 @@ def querymixtureGP_block(Xq, group, a, eta, root, levels, radius, delta, weight_
 def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None,
                           method="dense"):
     """posterior draws of the R latent blended fields at Xq -> (draws [n_draws, Nq, R] as a torch device tensor, jitter).
-    The joint covariance of querymixtureGP_cov_multi is factored once (torch.linalg.cholesky_ex, the jitter ladder of
+    The joint covariance of querymixtureGP_cov_multi is factored once (_dense_draw: torch's Cholesky, the jitter ladder of
     samplemixtureGP) and serves every column: draws[:, :, c] = Yq[:, c] + z[:, :, c] L^T with independent standard normals
     per column.  z [n_draws, Nq, R]: the normals to use; otherwise they are drawn from `generator`.  A covariance that
     holds NaN (a batch that blends a patch whose factorisation failed or whose trend is flagged) raises LinAlgError
@@ -1994,48 +2008,19 @@ def samplemixtureGP_multi(Xq, eta, root, levels, radius, delta, weight_theta, n_
 
     if method not in ("dense", "blocks"):
         raise ValueError("method must be \"dense\" or \"blocks\", not %r" % (method,))
+    who = "samplemixtureGP_multi"
     if method == "blocks":
-        who = "samplemixtureGP_multi"
-        _refuse_closure_kernel(weight_theta, who)
-        theta = getattr(getattr(eta, "_model", None), "theta", None)
-        if theta is not None:
-            _refuse_closure_kernel(theta, who)
-        q = _patches_query(Xq, eta, root, radius, delta, who)
-        q.model._need(multi=True)
-        q.items_multi_fitted(True)
-        q.mix_multi(weight_theta)
-        Yq = torch.empty((int(q.model.R), q.Nq), dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))
-        q.fetch_multi_into(Yq.T)
+        q = _fitted_query(Xq, eta, root, radius, delta, weight_theta, who, True)
+    else:
+        q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, who)
+    R = int(q.model.R)
+    Yq = torch.empty((R, q.Nq), dtype=torch.float64, device=torch.device("cuda", q.model.ctx.device))  # column-major (Nq, R)
+    q.fetch_multi_into(Yq.T)
+    if method == "blocks":
         E, jitter = _sample_blocks(q, True, weight_theta, n_draws, generator, z, who)
         return Yq.T[None, :, :] + E, jitter
-    q = _cov_multi_query(Xq, eta, root, radius, delta, weight_theta, "samplemixtureGP_multi")
-    dev = torch.device("cuda", q.model.ctx.device)
-    Nq, R = q.Nq, int(q.model.R)
-    Cov = torch.empty((Nq, Nq), dtype=torch.float64, device=dev)
-    Yq = torch.empty((R, Nq), dtype=torch.float64, device=dev)          # column-major (Nq, R)
-    q.fetch_multi_into(Yq.T)
-    q.fetch_cov_into(Cov)
-    q.model.ctx.synchronize()                   # the copies ran on the context's stream, torch reads on its own
-    if not bool(torch.isfinite(Cov).all()):
-        raise np.linalg.LinAlgError("samplemixtureGP_multi: the joint covariance holds NaN or Inf entries: a query of the "
-                                    "batch blends a patch whose factorisation failed (DeviceModel.info()) or whose trend "
-                                    "is flagged (DeviceModel.trend_info())")
-    scale = float(torch.trace(Cov)) / max(Nq, 1)
-    jitter, eye = 0.0, torch.eye(Nq, dtype=torch.float64, device=dev)
-    while True:
-        L, info = torch.linalg.cholesky_ex(Cov + jitter * eye if jitter else Cov)
-        if int(info) == 0:
-            break
-        jitter = 2.0 ** -52 * scale if jitter == 0.0 else 10.0 * jitter
-        if not jitter <= 2.0 ** -26 * scale:
-            raise np.linalg.LinAlgError("samplemixtureGP_multi: the joint covariance is not positive definite with a "
-                                        "jitter of up to 2^-26 trace / Nq")
-    if z is None:
-        z = torch.randn((int(n_draws), Nq, R), dtype=torch.float64, device=dev, generator=generator)
-    else:
-        z = torch.as_tensor(z, dtype=torch.float64, device=dev)
-        if tuple(z.shape) != (int(n_draws), Nq, R):
-            raise ValueError("z must have shape (%d, %d, %d), not %s" % (int(n_draws), Nq, R, tuple(z.shape)))
+    L, z, jitter = _dense_draw(q, n_draws, R, generator, z, who, "whose factorisation failed (DeviceModel.info()) or whose "
+                               "trend is flagged (DeviceModel.trend_info())")
     # column by column, each as samplemixtureGP takes its draws
     return torch.stack([Yq[c][None, :] + z[:, :, c] @ L.T for c in range(R)], dim=2), jitter
 
@@ -2050,6 +2035,14 @@ def querymixtureGP_multi_patches(Xq, eta, root, levels, radius, delta, weight_th
     return q.fetch_multi(q.model.R)
 
 
+def _first_best(scores, all_nan):
+    """the index of the first of the highest scores; a NaN never wins, and if every score is NaN ValueError(all_nan)"""
+    valid = np.nonzero(~np.isnan(scores))[0]
+    if len(valid) == 0:
+        raise ValueError(all_nan)
+    return int(valid[int(np.argmax(scores[valid]))])               # argmax: the first of equal maxima
+
+
 def select_candidates(scores):
     """winner per patch of a [G, P] score array (higher is better) -> int64 [P].  Ties go to the lowest candidate index,
     a NaN never wins, and a patch whose scores are all NaN raises ValueError naming the patch."""
@@ -2058,11 +2051,7 @@ def select_candidates(scores):
         raise ValueError("scores must be a [G, P] array with G >= 1")
     winners = np.empty(scores.shape[1], dtype=np.int64)
     for r in range(scores.shape[1]):
-        col = scores[:, r]
-        valid = np.nonzero(~np.isnan(col))[0]
-        if len(valid) == 0:
-            raise ValueError("patch %d: every candidate scored NaN (no candidate could be factorised)" % r)
-        winners[r] = valid[int(np.argmax(col[valid]))]             # argmax: the first of equal maxima
+        winners[r] = _first_best(scores[:, r], "patch %d: every candidate scored NaN (no candidate could be factorised)" % r)
     return winners
 
 
@@ -2095,7 +2084,7 @@ def selectmixtureGP_(eta, y_parts, candidates, score="evidence"):
         model.info()                     # failed patches score NaN below: the library reports them as NaN
         if score == "evidence":
             logdet, quad = model.evidence()
-            scores[g] = -0.5 * quad - 0.5 * logdet - 0.5 * model.n * np.log(2.0 * np.pi)
+            scores[g] = _log_evidence(logdet, quad, model.n)
         else:
             model.loo()
             res, var = model.loo_values()
@@ -2130,6 +2119,32 @@ def _blend_query(model, X, who):
     return q
 
 
+def _blend_loo(model, q, radius, delta, weight_theta, noisy, variance=None):
+    """one blended leave-one-out on the query of _blend_query -> what its fetch returns: loo() if it is stale, the plan,
+    the items, the blend.  variance=None: the single-output path; else the R columns, with or without the variance"""
+    if not model._loo_done:
+        model.loo()
+    q.plan(radius, delta)
+    if variance is None:
+        q.items_loo(noisy)
+        q.mix(weight_theta)
+        return q.fetch()
+    q.items_loo_multi(noisy, variance)
+    q.mix_multi(weight_theta)
+    return q.fetch_multi(model.R)
+
+
+def _blend_scores(model, q, candidates, R, score):
+    """scores [G] (R=None) or [G, R] of the candidates (radius, delta, weight_theta): score(mu, var) of the blended
+    leave-one-out with the noisy variances.  One query object, re-planned per candidate."""
+    scores = np.empty(len(candidates) if R is None else (len(candidates), R))
+    for g, (radius, delta, weight_theta) in enumerate(candidates):
+        mu, var = _blend_loo(model, q, radius, delta, weight_theta, True, None if R is None else True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scores[g] = score(mu, var)
+    return scores
+
+
 def loomixtureGP_blend(eta, root, radius, delta, weight_theta, X=None, noisy=False):
     """leave-one-out of the BLENDED predictor -> (mu_loo, var_loo), N values each: what querymixtureGP_patches would
     predict at training point j had the model been fitted without j, the tree held fixed.  No refit: one plan, a lookup
@@ -2139,12 +2154,7 @@ def loomixtureGP_blend(eta, root, radius, delta, weight_theta, X=None, noisy=Fal
     of the observation (each patch's sigma2 included) rather than of the latent field.  Runs loo() if it is stale."""
     model = _blend_model(eta, "loomixtureGP_blend")
     q = _blend_query(model, X, "loomixtureGP_blend")
-    if not model._loo_done:
-        model.loo()
-    q.plan(radius, delta)
-    q.items_loo(noisy)
-    q.mix(weight_theta)
-    return q.fetch()
+    return _blend_loo(model, q, radius, delta, weight_theta, noisy)
 
 
 def selectblendGP_(eta, root, y, candidates, X=None):
@@ -2160,20 +2170,8 @@ def selectblendGP_(eta, root, y, candidates, X=None):
     if y.shape != (model.N,):
         raise ValueError("y must hold the %d global targets" % model.N)
     q = _blend_query(model, X, "selectblendGP_")
-    if not model._loo_done:
-        model.loo()
-    scores = np.empty(len(candidates))
-    for g, (radius, delta, weight_theta) in enumerate(candidates):
-        q.plan(radius, delta)
-        q.items_loo(True)
-        q.mix(weight_theta)
-        mu, var = q.fetch()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            scores[g] = loo_log_pseudo_likelihood(y - mu, var)
-    valid = np.nonzero(~np.isnan(scores))[0]
-    if len(valid) == 0:
-        raise ValueError("every candidate scored NaN")
-    return scores, int(valid[int(np.argmax(scores[valid]))])
+    scores = _blend_scores(model, q, candidates, None, lambda mu, var: loo_log_pseudo_likelihood(y - mu, var))
+    return scores, _first_best(scores, "every candidate scored NaN")
 
 
 # ---- the same for the multi-output path: R target columns, with or without a trend (fitmixtureGP_multi_ / _trend_)
@@ -2194,12 +2192,7 @@ def loomixtureGP_blend_multi(eta, root, radius, delta, weight_theta, X=None, noi
     in var: without it the patch has fewer points than basis functions, so the prediction does not exist."""
     model = _blend_multi_model(eta, "loomixtureGP_blend_multi")
     q = _blend_query(model, X, "loomixtureGP_blend_multi")
-    if not model._loo_done:
-        model.loo()
-    q.plan(radius, delta)
-    q.items_loo_multi(noisy, variance)
-    q.mix_multi(weight_theta)
-    return q.fetch_multi(model.R)
+    return _blend_loo(model, q, radius, delta, weight_theta, noisy, bool(variance))
 
 
 def selectblendGP_multi_(eta, root, Y, candidates, X=None):
@@ -2217,18 +2210,6 @@ def selectblendGP_multi_(eta, root, Y, candidates, X=None):
     if Y.shape != (model.N, model.R):
         raise ValueError("Y must hold the %d x %d global targets" % (model.N, model.R))
     q = _blend_query(model, X, "selectblendGP_multi_")
-    if not model._loo_done:
-        model.loo()
-    scores = np.empty((len(candidates), model.R))
-    for g, (radius, delta, weight_theta) in enumerate(candidates):
-        q.plan(radius, delta)
-        q.items_loo_multi(True, True)
-        q.mix_multi(weight_theta)
-        MU, var = q.fetch_multi(model.R)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            scores[g] = [loo_log_pseudo_likelihood(Y[:, c] - MU[:, c], var) for c in range(model.R)]
-    rows = scores.sum(axis=1)
-    valid = np.nonzero(~np.isnan(rows))[0]
-    if len(valid) == 0:
-        raise ValueError("every candidate scored NaN")
-    return scores, int(valid[int(np.argmax(rows[valid]))])
+    scores = _blend_scores(model, q, candidates, model.R, lambda MU, var: [
+        loo_log_pseudo_likelihood(Y[:, c] - MU[:, c], var) for c in range(model.R)])
+    return scores, _first_best(scores.sum(axis=1), "every candidate scored NaN")

@@ -109,6 +109,53 @@ def test_a_new_fit_makes_the_blended_scores_stale():
         q.items_loo()
 
 
+class _OkLib:
+    """stands in for the loaded library: every call succeeds and writes nothing"""
+
+    def __getattr__(self, name):
+        return lambda *a: 0
+
+
+MODEL_MIRROR = ("_from_tree", "_all_leaves", "_has_factor", "_has_targets", "_has_kernels", "_loo_done", "_multi_solved",
+                "R", "_X", "_X_global", "_index", "theta", "sigma2")
+QUERY_MIRROR = ("Xq", "has_diag", "total", "first_owned", "num_owned", "R_items", "variance", "grad_items", "vgrad_items",
+                "block_F", "block_variance")
+
+
+def test_every_birth_of_a_query_carries_the_same_mirror():
+    """the constructor, from_items and a bare object.__new__ differ only in what the birth itself knows: the host copy of
+    the points and, for from_items, the item counts"""
+    m = _query().model
+    m.ctx.L, m.D = _OkLib(), 2
+    born = {"constructor": _DeviceQuery(m, np.zeros((6, 2))), "from_items": _DeviceQuery.from_items(m, 6, None, None),
+            "bare": object.__new__(_DeviceQuery)}
+    for how, q in born.items():
+        for name in QUERY_MIRROR:
+            assert hasattr(q, name), (how, name)
+    for name in set(QUERY_MIRROR) - {"Xq", "total", "num_owned"}:
+        assert len({getattr(q, name) for q in born.values()}) == 1, name
+    assert born["constructor"].Xq.shape == (6, 2) and born["from_items"].Xq is None and born["bare"].Xq is None
+    assert (born["constructor"].total, born["constructor"].num_owned) == (0, 0)         # until plan()
+    assert (born["from_items"].total, born["from_items"].num_owned) == (6, 6)
+    assert born["constructor"].Nq == born["from_items"].Nq == 6
+    bare = object.__new__(_DeviceModel)
+    for name in MODEL_MIRROR:
+        assert hasattr(bare, name), name
+
+
+@pytest.mark.parametrize("change", [
+    lambda m: m.reserve(3),
+    lambda m: m._append(np.zeros((1, 2)), np.zeros(1), None, np.array([1], dtype=np.int32), None),
+    lambda m: m._remove(np.array([0], dtype=np.int32), np.array([2], dtype=np.int64)),
+], ids=["reserve", "append", "remove"])
+def test_changed_rows_make_loo_and_the_columns_stale_and_keep_the_factor(change):
+    m = _query(_multi_solved=True, R=3, n=np.array([5, 7])).model
+    m.ctx.L = _OkLib()
+    change(m)
+    assert (m._loo_done, m._multi_solved, m.R) == (False, False, 0)
+    assert m._has_factor and m._has_kernels
+
+
 @pytest.mark.parametrize("fn", ["loomixtureGP_blend", "selectblendGP_"])
 def test_module_functions_need_a_fitted_tree_model(fn, monkeypatch):
     def no_device(*a, **k):
