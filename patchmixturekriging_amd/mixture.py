@@ -1921,13 +1921,13 @@ def _sample_blocks(q, multi, weight_theta, n_draws, generator, z, who):
     jitter = float(jit.max()) if P else 0.0
     n, total = int(n_draws), int(q.total)
     z = _normals(z, (n, total) if R is None else (n, total, R), dev, generator)
-    torch.cuda.synchronize(dev)                 # torch wrote z on its own stream, the library reads on the context's
-    if R is None:
-        E = q.draw(weight_theta, z.contiguous())
-    else:
-        E = torch.stack([q.draw(weight_theta, z[:, :, c].contiguous()) for c in range(R)], dim=2)
-    q.model.ctx.synchronize()
-    return E, jitter
+    # every column's normals as one contiguous array, made before the first draw and held until the last has run: torch
+    # writes them (and would reuse a freed one's memory) on its own stream, the library reads on the context's
+    cols = [z.contiguous()] if R is None else [z[:, :, c].contiguous() for c in range(R)]
+    torch.cuda.synchronize(dev)
+    E = [q.draw(weight_theta, zc) for zc in cols]
+    q.model.ctx.synchronize()                   # the draws are enqueued: torch reads them after this
+    return (E[0] if R is None else torch.stack(E, dim=2)), jitter
 
 
 def samplemixtureGP(Xq, eta, root, levels, radius, delta, weight_theta, n_draws, generator=None, z=None, method="dense"):
