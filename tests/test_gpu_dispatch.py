@@ -1,5 +1,6 @@
 """Launch dispatch coverage: every (D, FAM, PP, dtype) instantiation behind launch_kernel_matrix_slabs, launch_items and
-launch_items_multi (pmk_dispatch.h) is reached, and is the right one.
+launch_items_multi (pmk_dispatch.h) is reached, and is the right one.  The four launchers that came later (launch_items_grad,
+launch_items_vgrad, launch_items_cov, launch_items_block): tests/test_gpu_dispatch_stages.py.
 
 One launcher per kernel takes `th`: a descriptor (PP = false, FAM from that descriptor) or null for the model's device
 arrays (PP = true, FAM from the model).  The uniform and the per-patch instantiation are the same instruction stream
